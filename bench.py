@@ -2,7 +2,17 @@
 (BASELINE.json metric; SURVEY.md §8d config 4, and config 5 across GPUs).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--pairs P] [--lanes L]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run sets up, warms up, times the K steps and prints the result line
+(metric, value, unit, ms_per_step, config, timed_region).  `--dump-outputs
+DIR` also writes the flows that the last timed step left in its device slots
+to DIR/flows.npy (float32 (P, 2, H, W); beyond DUMP_BYTES a fixed seeded
+sample of the same pixels of every pair, (P, 2, n)); the inputs are
+synth_pair(H, W, seed k), identical from run to run.  Everything under
+"Reported beside it" and "Also reported" below runs, after the timed steps,
+only with `--full`.
 
 One process per GPU.  `--gpus N` with N > 1 and no launcher around it
 (WORLD_SIZE unset) starts `python -m torch.distributed.run --nproc-per-node N
@@ -20,7 +30,7 @@ waited for, so the lanes do not drain between steps; the steps alternate
 between two sets of P slots); for N > 1 each step's flows are also gathered
 to rank 0 with RCCL over xGMI (of_rccl_gather_slots).  Timed region: barrier
 + device sync on both sides, max over ranks.  value = pairs processed by all
-ranks / time (weak scaling: P pairs per GPU).  Reported beside it:
+ranks / time (weak scaling: P pairs per GPU).  Reported beside it (--full):
 `device_resident_drained` (the same steps as one of_pairs_run call each:
 the lanes drain at every step end), `host_to_host` (SURVEY.md §8d's form:
 uint8 frames in host memory -> H2D -> ... -> D2H of the fp32 flow,
@@ -29,7 +39,7 @@ never `value` -- the task's measurement contract puts the inputs in HBM)
 and `streamed` (host-to-host through the pool, of_pairs_submit /
 of_pairs_wait); all over the same K steps.
 
-Also reported (one JSON line on rank 0):
+Also reported with --full (one JSON line on rank 0):
   roofline      dominant HBM kernel: algorithmic bytes per launch / mean
                 HIP-event duration of that kernel over a profiled replay of
                 the step's pairs one at a time (lanes = 1; the lanes replay
@@ -108,9 +118,16 @@ def parse(argv=None):
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--method", default="classic+nl-fast")
     ap.add_argument("--solver", default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-profile", action="store_true")
-    ap.add_argument("--no-stream", action="store_true", help="skip the streamed (pair pool) rate")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and check everything else the line can carry: the "
+                         "drained, host-to-host and streamed rates, per-level times, AEPE, the roofline replays "
+                         "and the CPU baseline (each still switched off by its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the flows of the last timed step to DIR/flows.npy (float32; a fixed seeded "
+                         "pixel sample when they exceed DUMP_BYTES)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-profile", action="store_true", help="--full: skip the profiled replays (roofline)")
+    ap.add_argument("--no-stream", action="store_true", help="--full: skip the streamed (pair pool) rate")
     ap.add_argument("--cpu-sample", type=int, default=360, help="crop height of the CPU-baseline sample")
     ap.add_argument("--sor-pipeline", type=int, default=None,
                     help="OF_OPT_SOR_PIPELINE for 'sor' (0 per sweep, 1 pipelined, 2 + one-workgroup small levels)")
@@ -215,6 +232,46 @@ def run_step(ctx, P0, nslots, lanes):
     """estimate_flow on device slots 0..nslots-1, `lanes` pairs in flight
     (each lane its own HIP stream + host thread inside the library)."""
     ctx.check(ctx.lib.of_pairs_run(ctx.handle, nslots, C.byref(P0), lanes, None))
+
+
+def make_frames(H, W, seeds):
+    """synth_pair of every seed as uint8 frames (what a caller holds) plus the
+    analytic ground truth; one thread per pair (numpy releases the GIL), the
+    arrays are the serial loop's bit for bit."""
+    from concurrent.futures import ThreadPoolExecutor
+    with ThreadPoolExecutor(max(1, min(len(seeds), 16))) as ex:
+        trip = list(ex.map(lambda seed: synth_pair(H, W, seed), seeds))
+    f1 = [np.ascontiguousarray(im1.astype(np.uint8)) for im1, _, _ in trip]
+    f2 = [np.ascontiguousarray(im2.astype(np.uint8)) for _, im2, _ in trip]
+    return f1, f2, [gt for _, _, gt in trip]
+
+
+DUMP_BYTES = 48 * 2 ** 20  # --dump-outputs writes at most this much over all ranks
+DUMP_SEED = 20240
+
+
+def dump_sample(flows, budget):
+    """(P, 2, H, W) as it is when it fits `budget` bytes, else (P, 2, n): the
+    same n pixels of every pair, drawn without replacement by a fixed seed
+    (so two builds dump the same pixels) and kept in raster order."""
+    P, _, H, W = flows.shape
+    n = budget // (P * 2 * flows.itemsize)
+    if n >= H * W:
+        return flows
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(H * W, size=int(n), replace=False))
+    return np.ascontiguousarray(flows.reshape(P, 2, H * W)[:, :, idx])
+
+
+def dump_outputs(ctx, lib, path, first_slot, pairs, H, W, world, rank):
+    """The flows the timed path left in the device slots of its last step,
+    as a caller would download them (of_pair_download), to DIR/flows.npy
+    (DIR/flows_rank<r>.npy for N > 1: each rank its own pairs)."""
+    flows = np.empty((pairs, 2, H, W), dtype=np.float32)
+    for s in range(pairs):
+        ctx.check(lib.of_pair_download(ctx.handle, first_slot + s, _native.ptr(flows[s])))
+    os.makedirs(path, exist_ok=True)
+    name = "flows.npy" if world == 1 else f"flows_rank{rank}.npy"
+    np.save(os.path.join(path, name), dump_sample(flows, DUMP_BYTES // world))
 
 
 def flow_digests(outs):
@@ -608,12 +665,7 @@ def main(argv=None):
     # host frames (uint8, what a caller holds) and host flow buffers; the
     # same pairs also uploaded once to device slots for the device-resident rate
     seeds = shard_seeds(rank, args.pairs)
-    gts, f1, f2 = [], [], []
-    for seed in seeds:
-        im1, im2, gt = synth_pair(H, W, seed)
-        gts.append(gt)
-        f1.append(np.ascontiguousarray(im1.astype(np.uint8)))
-        f2.append(np.ascontiguousarray(im2.astype(np.uint8)))
+    f1, f2, gts = make_frames(H, W, seeds)
     outs = [np.empty((2, H, W), dtype=np.float32) for _ in seeds]
     vp = C.c_void_p
     p1 = (vp * args.pairs)(*[x.ctypes.data for x in f1])
@@ -679,8 +731,49 @@ def main(argv=None):
     elapsed = max_over_ranks(dist, time.perf_counter() - t0)
     value = world * NP * args.steps / elapsed
     ctx.check(lib.of_pairs_close(ctx.handle))
+    last_set = ((args.steps - 1) % 2) * NP  # first slot of the last timed step's set
+    if args.dump_outputs:
+        dump_outputs(ctx, lib, args.dump_outputs, last_set, NP, H, W, world, rank)
+
+    # the result line of a plain run; --full adds to it below
+    head = {
+        "metric": metric_name(args),
+        "value": round(value, 4), "unit": "pairs/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(1e3 * elapsed / args.steps, 3), "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": f"{args.method} on synth_pair({H},{W},seed) RGB, {args.pairs} pair(s)/GPU/step, "
+                               f"{min(args.lanes, args.pairs)} in flight",
+                   "method": args.method, "height": H, "width": W, "pairs_per_gpu": args.pairs,
+                   "lanes": min(args.lanes, args.pairs),
+                   "solver": args.solver or "backslash (GPU block-Jacobi PCG surrogate)",
+                   "parallelism": f"pairs sharded 1/GPU x {world}, RCCL gather"
+                                  + (" (one-rank proxy, --rccl-self)" if args.rccl_self else "")},
+        "rccl_nranks": rccl_nranks if gathering else None,
+        "rccl_gather_per_step": bool(gathering),
+        "timed_region": "frames resident in HBM (device slots, uploaded before the timed region) -> "
+                        "flows (fp32) left in HBM; K steps queued back to back through the pair pool "
+                        "(of_pairs_submit_slots), each step's flows gathered to rank 0 over RCCL when "
+                        "rccl_gather_per_step (N > 1, or --rccl-self); round 5 on: the steps overlap (before "
+                        "round 5 each step drained its lanes -- compare those rounds with "
+                        "device_resident_drained of a --full run)",
+        "full": bool(args.full),
+    }
+
+    def finish():
+        if gathering:
+            lib.of_rccl_finalize(ctx.handle)
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return 0
+
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(head), flush=True)
+        return finish()
+
     dev_uv = np.empty((2, H, W), dtype=np.float32)  # the timed flow of pair 0 (last step's slot set)
-    ctx.check(lib.of_pair_download(ctx.handle, ((args.steps - 1) % 2) * NP, _native.ptr(dev_uv)))
+    ctx.check(lib.of_pair_download(ctx.handle, last_set, _native.ptr(dev_uv)))
 
     # the same steps as one of_pairs_run call each (lanes drain at step end)
     def step():
@@ -817,26 +910,8 @@ def main(argv=None):
         cpu = cpu_baseline(args)
 
     if rank == 0:
-        line = {
-            "metric": metric_name(args),
-            "value": round(value, 4), "unit": "pairs/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(1e3 * elapsed / args.steps, 3), "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": f"{args.method} on synth_pair({H},{W},seed) RGB, {args.pairs} pair(s)/GPU/step, "
-                                   f"{min(args.lanes, args.pairs)} in flight",
-                       "method": args.method, "height": H, "width": W, "pairs_per_gpu": args.pairs,
-                       "lanes": min(args.lanes, args.pairs),
-                       "solver": args.solver or "backslash (GPU block-Jacobi PCG surrogate)",
-                       "parallelism": f"pairs sharded 1/GPU x {world}, RCCL gather"
-                                      + (" (one-rank proxy, --rccl-self)" if args.rccl_self else "")},
-            "rccl_nranks": rccl_nranks if gathering else None,
-            "rccl_gather_per_step": bool(gathering),
-            "timed_region": "frames resident in HBM (device slots, uploaded before the timed region) -> "
-                            "flows (fp32) left in HBM; K steps queued back to back through the pair pool "
-                            "(of_pairs_submit_slots), each step's flows gathered to rank 0 over RCCL when "
-                            "rccl_gather_per_step (N > 1, or --rccl-self); round 5 on: the steps overlap (before "
-                            "round 5 each step drained its lanes -- compare those rounds with "
-                            "device_resident_drained)",
+        line = dict(head)
+        line.update({
             "device_resident_drained": {"value": round(world * NP * args.steps / d_elapsed, 4),
                                         "ms_per_step": round(1e3 * d_elapsed / args.steps, 3),
                                         "steps": args.steps,
@@ -871,14 +946,9 @@ def main(argv=None):
             # as timed, where durations include co-running lanes' kernels
             "kernel_ms_per_pair_isolated": kms(kt_iso, args.pairs),
             "kernel_ms_per_pair_concurrent": kms(ktimes, args.pairs),
-        }
+        })
         print(json.dumps(line), flush=True)
-    if gathering:
-        lib.of_rccl_finalize(ctx.handle)
-    if dist is not None:
-        dist.barrier()
-        dist.destroy_process_group()
-    return 0
+    return finish()
 
 
 if __name__ == "__main__":

@@ -587,8 +587,15 @@ def gen_bags():
     """The reference's method objects as attribute bags (class name + every
     instance attribute except the image slots and the conv-matrix cache) for
     the 12 registry names and BAG_OVERRIDES, after parse_input_parameter —
-    the input of tools/reference_hook.py:of_params_from."""
+    the input of tools/reference_hook.py:of_params_from.  `hook_bytes` is
+    what the hook, loaded beside the reference's package as
+    optical_flow._mi355x, flattens the live object to (the of_params record,
+    hex): tests/test_reference_hook.py holds the bag to it."""
     import json
+    spec = importlib.util.spec_from_file_location(
+        "optical_flow._mi355x", os.path.join(HERE, "..", "..", "tools", "reference_hook.py"))
+    hook = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(hook)
     cases = {m: (m, None) for m in METHODS}
     cases.update(BAG_OVERRIDES)
     out = {}
@@ -599,7 +606,8 @@ def gen_bags():
         attrs = {k: _enc(v) for k, v in vars(o).items() if k not in ("images", "_cached_conv_mats")}
         out[tag] = {"method": m, "params": _enc(prm) if not isinstance(prm, dict) else
                     {k: _enc(v) for k, v in prm.items()},
-                    "class": type(o).__name__, "attrs": attrs}
+                    "class": type(o).__name__, "attrs": attrs,
+                    "hook_bytes": bytes(hook.of_params_from(o)).hex()}
     path = os.path.join(HERE, "ref_bags.json")
     with open(path, "w") as f:
         json.dump(out, f, indent=1, sort_keys=True)

@@ -207,3 +207,31 @@ def test_bench_world_size_mismatch_refused():
     assert "WORLD_SIZE=2 but --gpus 1" in r.stderr
     r, recs = _run_bench(["--gpus", "2", "--rccl-self", "--dry-run"], _bench_env(WORLD_SIZE="2"))
     assert r.returncode == 2 and not recs
+
+
+def test_bench_dump_sample_and_frames():
+    """--dump-outputs: flows within the byte budget are written whole; larger
+    ones as the same seeded, raster-ordered pixels of every pair, the same
+    from call to call and within the budget.  The threaded frame generation
+    returns synth_pair's arrays bit for bit."""
+    import numpy as np
+
+    import bench
+    from optical_flow.utils.synthetic import synth_pair
+    flows = np.random.default_rng(1).random((3, 2, 17, 23)).astype(np.float32)
+    assert bench.dump_sample(flows, flows.nbytes) is flows
+    s = bench.dump_sample(flows, flows.nbytes // 2)
+    assert s.dtype == np.float32 and s.shape == (3, 2, 17 * 23 // 2) and s.nbytes <= flows.nbytes // 2
+    np.testing.assert_array_equal(s, bench.dump_sample(flows.copy(), flows.nbytes // 2))
+    idx = np.sort(np.random.default_rng(bench.DUMP_SEED).choice(17 * 23, size=s.shape[2], replace=False))
+    assert len(set(idx)) == len(idx)
+    np.testing.assert_array_equal(s, flows.reshape(3, 2, -1)[:, :, idx])
+    # 8 pairs at 1080p (the default run) stay under 64 MB
+    assert bench.DUMP_BYTES <= 64e6
+    f1, f2, gts = bench.make_frames(20, 28, [4, 0, 7])
+    for k, seed in enumerate([4, 0, 7]):
+        a, b, gt = synth_pair(20, 28, seed)
+        assert f1[k].dtype == np.uint8 and f1[k].flags.c_contiguous
+        np.testing.assert_array_equal(f1[k], a.astype(np.uint8))
+        np.testing.assert_array_equal(f2[k], b.astype(np.uint8))
+        np.testing.assert_array_equal(gts[k], gt)

@@ -358,3 +358,44 @@ def test_pool_refuses_settings_and_busy_slots():
     v = C.c_int64(-1)
     ctx.check(lib.of_get_option(ctx.handle, _abi.OF_OPT_RCCL_NRANKS, C.byref(v)))
     assert v.value == 0  # no communicator on this context
+
+
+def test_bench_dump_outputs_are_the_timed_flows(tmp_path, capsys):
+    """bench.py --dump-outputs: a plain run (no --full) prints the headline
+    line, with --steps timed steps, and DIR/flows.npy holds the flows of the
+    last timed step: float32 (P, 2, H, W), bitwise of_pairs_run's on the same
+    pairs with the same lanes (the pool's contract above); a second run with
+    the same arguments writes the same bytes."""
+    import json
+
+    import bench
+    from optical_flow import _native
+    from optical_flow.utils.synthetic import synth_pair
+    H, W, n, lanes = 60, 88, 3, 2
+    argv = ["--gpus", "1", "--steps", "3", "--warmup", "1", "--height", str(H), "--width", str(W),
+            "--pairs", str(n), "--lanes", str(lanes)]
+    dumps = []
+    for d in ("a", "b"):
+        assert bench.main(argv + ["--dump-outputs", str(tmp_path / d)]) == 0
+        recs = [json.loads(ln) for ln in capsys.readouterr().out.splitlines() if ln.startswith('{"metric"')]
+        assert len(recs) == 1
+        rec = recs[0]
+        assert rec["steps"] == 3 and rec["warmup"] == 1 and rec["full"] is False
+        assert rec["unit"] == "pairs/s" and rec["higher_is_better"] is True and rec["dtype"] == "f32"
+        assert rec["value"] == pytest.approx(n * 1e3 / rec["ms_per_step"], rel=1e-3)
+        assert "roofline" not in rec and "cpu_baseline" not in rec and "host_to_host" not in rec
+        assert [p.name for p in (tmp_path / d).iterdir()] == ["flows.npy"]
+        dumps.append(np.load(tmp_path / d / "flows.npy"))
+    assert dumps[0].dtype == np.float32 and dumps[0].shape == (n, 2, H, W)
+    np.testing.assert_array_equal(dumps[0], dumps[1])
+    ctx = _native.Context(0)
+    for s in range(n):
+        a, b, _ = synth_pair(H, W, s)
+        ctx.check(ctx.lib.of_pair_upload(ctx.handle, s, _native.ptr(_native.f32(a)), _native.ptr(_native.f32(b)),
+                                         H, W, 3))
+    ctx.check(ctx.lib.of_pairs_run(ctx.handle, n, C.byref(_params("classic+nl-fast")), lanes, None))
+    for s in range(n):
+        uv = np.empty((2, H, W), np.float32)
+        ctx.check(ctx.lib.of_pair_download(ctx.handle, s, _native.ptr(uv)))
+        np.testing.assert_array_equal(dumps[0][s], uv, err_msg=f"pair {s}")
+    ctx.close()

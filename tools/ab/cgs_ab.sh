@@ -13,6 +13,6 @@ for rep in 1 2; do for L in "$@"; do
 done; done
 for rep in 1 2; do for L in "$@"; do
   echo "== $L rep $rep" >> $O/bench_ab.log
-  OPTFLOW_LIB=$L tools/gpu_step.sh 300 $O/tmp.log python -u bench.py --steps 10 --no-cpu-baseline --no-profile || exit $?
+  OPTFLOW_LIB=$L tools/gpu_step.sh 300 $O/tmp.log python -u bench.py --full --steps 10 --no-cpu-baseline --no-profile || exit $?
   grep '^{' $O/tmp.log >> $O/bench_ab.log
 done; done

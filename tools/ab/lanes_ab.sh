@@ -7,6 +7,6 @@ export PYTHONDONTWRITEBYTECODE=1
 O=gpurun_out/$TAG; mkdir -p $O
 for rep in 1 2; do for L in "$@"; do
   echo "== lanes $L rep $rep" >> $O/lanes_ab.log
-  tools/gpu_step.sh 300 $O/bench_tmp.log python -u bench.py --steps 6 --lanes $L --no-cpu-baseline --no-profile || exit $?
+  tools/gpu_step.sh 300 $O/bench_tmp.log python -u bench.py --full --steps 6 --lanes $L --no-cpu-baseline --no-profile || exit $?
   grep '^{' $O/bench_tmp.log >> $O/lanes_ab.log
 done; done

@@ -14,6 +14,6 @@ fi
 OPTFLOW_LIB=$B tools/gpu_step.sh 300 $O/smoke.log python -u -c "import __graft_entry__ as g; g.smoke()" || exit $?
 for rep in 1 2; do for L in $A $B; do
   echo "== $L rep $rep" >> $O/bench_ab.log
-  OPTFLOW_LIB=$L tools/gpu_step.sh 300 $O/bench_tmp.log python -u bench.py --steps 6 --no-cpu-baseline --no-profile || exit $?
+  OPTFLOW_LIB=$L tools/gpu_step.sh 300 $O/bench_tmp.log python -u bench.py --full --steps 6 --no-cpu-baseline --no-profile || exit $?
   grep '^{' $O/bench_tmp.log >> $O/bench_ab.log
 done; done

@@ -9,4 +9,4 @@ tools/gpu_step.sh 400 $O/tests.log python -u -m pytest -x -v --timeout 200 --tim
   tests/test_display.py tests/test_gpu_batch.py tests/test_pipeline.py -m gpu || exit $?
 tools/gpu_step.sh 400 $O/probe_dedicated.log python -u tools/order_probe.py 10 || exit $?
 OF_STREAM_QUEUE=shared tools/gpu_step.sh 400 $O/probe_shared.log python -u tools/order_probe.py 10 || exit $?
-tools/gpu_step.sh 300 $O/bench.log python -u bench.py --steps 20 --no-cpu-baseline --no-profile || exit $?
+tools/gpu_step.sh 300 $O/bench.log python -u bench.py --full --steps 20 --no-cpu-baseline --no-profile || exit $?

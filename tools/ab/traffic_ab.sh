@@ -8,7 +8,7 @@ set -u
 TAG=$1; KRE=$2; shift 2
 export PYTHONDONTWRITEBYTECODE=1 TMPDIR=/tmp
 O=gpurun_out/$TAG; mkdir -p $O
-S="bench.py --steps 1 --warmup 0 --pairs 1 --lanes 1 --no-cpu-baseline --no-profile --no-stream"
+S="bench.py --full --steps 1 --warmup 0 --pairs 1 --lanes 1 --no-cpu-baseline --no-profile --no-stream"
 i=0
 for L in "$@"; do
   D=$O/$i; mkdir -p $D; echo "$L" > $D/lib.txt
@@ -20,6 +20,6 @@ for L in "$@"; do
 done
 for rep in 1 2; do for L in "$@"; do
   echo "== $L rep $rep" >> $O/bench_ab.log
-  OPTFLOW_LIB=$L tools/gpu_step.sh 300 $O/bench_tmp.log python -u bench.py --steps 6 --no-cpu-baseline --no-profile || exit $?
+  OPTFLOW_LIB=$L tools/gpu_step.sh 300 $O/bench_tmp.log python -u bench.py --full --steps 6 --no-cpu-baseline --no-profile || exit $?
   grep '^{' $O/bench_tmp.log >> $O/bench_ab.log
 done; done
