@@ -255,6 +255,54 @@ int of_estimate_flow(of_ctx *ctx, of_params *params, const float *im1, const flo
 int of_compute_flow(of_ctx *ctx, of_params *params, const float *images, int H, int W, int nc,
                     const float *guide, int gc, const float *init_uv, float *out_uv, of_stats *stats);
 
+/*
+ * Forward-backward consistency of two flows (Sundaram et al. 2010): where can
+ * `fw` (frame 1 -> 2) be trusted, given `bw` (frame 2 -> 1)?  fw, bw planar
+ * 2 x H x W.  For pixel (i, j), 0-based, u = fw.x, v = fw.y, in double from
+ * the fp32 flows, no fma contraction, in exactly this order (a numpy float64
+ * restatement gives the same bits):
+ *   q = j + u;  r = i + v
+ *   inside = q >= 0 && q <= W-1 && r >= 0 && r <= H-1      (NaN / Inf: false)
+ *   !inside: state = 2, err = +inf
+ *   j0 = floor(q), i0 = floor(r); fc = q - j0; fr = r - i0
+ *   j1 = min(j0+1, W-1); i1 = min(i0+1, H-1)
+ *   bu = (1-fr)*((1-fc)*B[i0][j0].x + fc*B[i0][j1].x)
+ *      + fr*((1-fc)*B[i1][j0].x + fc*B[i1][j1].x);   bv the same with .y
+ *   du = u + bu; dv = v + bv;  err = du*du + dv*dv
+ *   thr = alpha1*((u*u + v*v) + (bu*bu + bv*bv)) + alpha2
+ *   state = err > thr ? 1 : 0
+ *   state : H x W bytes: 0 consistent, 1 inconsistent / occluded, 2 the
+ *           forward flow leaves the frame
+ *   err   : H x W fp32 (float)err, or NULL
+ * The usual thresholds are alpha1 = 0.01, alpha2 = 0.5.  The backward mask is
+ * the same call with fw and bw exchanged.  alpha1 / alpha2 negative or not
+ * finite: OF_EINVAL.
+ */
+int of_fb_consistency(of_ctx *ctx, const float *fw, const float *bw, int H, int W,
+                      double alpha1, double alpha2, uint8_t *state, float *err);
+
+/*
+ * of_estimate_flow in both directions plus the forward-backward masks, one
+ * call: out_fw equals of_estimate_flow(im1, im2), out_bw equals
+ * of_estimate_flow(im2, im1) (bitwise), state_fw / state_bw (H x W bytes,
+ * either may be NULL) equal of_fb_consistency(out_fw, out_bw) /
+ * (out_bw, out_fw).  Gray conversion, the structure-texture split (or the
+ * fc / plain scaling) and the image pyramids run once for both directions;
+ * the weighted median's colour guide (Lab of each direction's first frame,
+ * its /255 decision from that frame's own maximum) and its pyramids are
+ * built per direction.  The two directions run one after the other on the
+ * context's stream.  init_fw / init_bw: planar 2 x H x W or NULL (zeros).
+ * params->alpha is written back once (both passes start from the caller's
+ * value and end on the same one).  The progress callback reports the backward
+ * pass as a second compute_flow.  stats_fw (may be NULL) is charged the shared
+ * preprocessing and its total_ms is the whole call's wall time; stats_bw (may
+ * be NULL) has preprocess_ms = 0 and the backward schedule's wall time.
+ */
+int of_estimate_flow_bidir(of_ctx *ctx, of_params *params, const float *im1, const float *im2,
+                           int H, int W, int C, const float *init_fw, const float *init_bw,
+                           float *out_fw, float *out_bw, double alpha1, double alpha2,
+                           uint8_t *state_fw, uint8_t *state_bw, of_stats *stats_fw, of_stats *stats_bw);
+
 /* compute_flow_base() for one pyramid level with the given alpha (one call =
  * all warping iterations of the level; hs.py:109-142, ba.py:143-206,
  * classic_nl.py:200-277).  uv_in / out_uv planar 2 x H x W. */

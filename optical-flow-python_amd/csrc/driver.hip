@@ -96,6 +96,16 @@ struct Arena {
     chunks.push_back({p, cap, bytes});
     return p;
   }
+  // offsets of the chunks now; rewind(mark) frees what was allocated since
+  // (the caller has synchronised the stream that used it)
+  std::vector<size_t> mark() const {
+    std::vector<size_t> m;
+    for (const auto &c : chunks) m.push_back(c.off);
+    return m;
+  }
+  void rewind(const std::vector<size_t> &m) {
+    for (size_t k = 0; k < chunks.size(); ++k) chunks[k].off = k < m.size() ? m[k] : 0;
+  }
   void release() {
     for (auto &c : chunks) hipFree(c.p);
     chunks.clear();
@@ -1865,18 +1875,29 @@ void check_params(const of_params *P) {
   }
 }
 
-// compute_flow (hs.py:49-99, ba.py:57-138, classic_nl.py:89-198, alt_ba.py:81-187)
-// images: device 2nc planes; guide: device gc planes or p == nullptr;
-// uv_io: full-resolution flow (init in, result out).
-void compute_flow_dev(of_ctx *c, of_params *P, const Img &images, const Img &guide, F2 &uv_io, of_stats *st) {
-  check_params(P);
+// The pyramids one compute_flow runs on: the texture (or scaled) pair's for
+// the first GNC stage and for the later ones, and the weighted median's colour
+// guide's when Classic+NL has one
+struct FlowPyr {
+  std::vector<Img> pyr, gpyr, cpyr, cgpyr;
+  int levels = 0;
+  bool use_guide = false;
+};
+
+void guide_pyramids(of_ctx *c, const of_params *P, const Img &guide, FlowPyr &F) {
+  F.use_guide = P->method == OF_METHOD_CLASSIC_NL && guide.p;
+  if (F.use_guide) {
+    F.cpyr = build_pyramid(c, guide, F.levels, P->pyramid_spacing);
+    F.cgpyr = build_pyramid(c, guide, P->gnc_pyramid_levels, P->gnc_pyramid_spacing);
+  }
+}
+
+// compute_flow, first half: preprocessing and pyramids (hs.py:49-75,
+// ba.py:57-99, classic_nl.py:89-139, alt_ba.py:81-126)
+// images: device 2nc planes; guide: device gc planes or p == nullptr
+FlowPyr flow_pyramids(of_ctx *c, of_params *P, const Img &images, const Img &guide) {
   const int H = images.H, W = images.W, C = images.C, nc = C / 2;
   REQUIRE(nc >= 1 && nc <= OF_MAX_NC, OF_ENOTSUP, "1..4 channels per frame supported");
-  hipEvent_t t0 = timing_event(c), t1 = timing_event(c);
-  HIPCHK(hipEventRecord(t0, c->stream));
-  c->prog_t0 = std::chrono::steady_clock::now();
-  // preprocessing (under the lanes' token with OF_PRE_TOKEN)
-  std::unique_ptr<BigPhase> pre(new BigPhase(c, OF_PRE_TOKEN ? (double)H * W : 0.0));
   Img img;
   if (P->texture) {
     const double alp = (P->method == OF_METHOD_HS || P->method == OF_METHOD_ALT_BA) ? 0.95 : P->alp;
@@ -1902,15 +1923,22 @@ void compute_flow_dev(of_ctx *c, of_params *P, const Img &images, const Img &gui
     levels = auto_levels(H, W, P->pyramid_spacing);
   P->pyramid_levels = levels;
   REQUIRE(levels <= OF_MAX_LEVELS, OF_EINVAL, "too many pyramid levels");
-  std::vector<Img> pyr = build_pyramid(c, img, levels, P->pyramid_spacing), gpyr, cpyr, cgpyr;
-  if (P->method != OF_METHOD_HS) gpyr = build_pyramid(c, img, P->gnc_pyramid_levels, P->gnc_pyramid_spacing);
-  const bool use_guide = P->method == OF_METHOD_CLASSIC_NL && guide.p;
-  if (use_guide) {
-    cpyr = build_pyramid(c, guide, levels, P->pyramid_spacing);
-    cgpyr = build_pyramid(c, guide, P->gnc_pyramid_levels, P->gnc_pyramid_spacing);
-  }
-  HIPCHK(hipEventRecord(t1, c->stream));
-  pre.reset();
+  FlowPyr F;
+  F.levels = levels;
+  F.pyr = build_pyramid(c, img, levels, P->pyramid_spacing);
+  if (P->method != OF_METHOD_HS) F.gpyr = build_pyramid(c, img, P->gnc_pyramid_levels, P->gnc_pyramid_spacing);
+  guide_pyramids(c, P, guide, F);
+  return F;
+}
+
+// compute_flow, second half: the GNC x level schedule on given pyramids
+// (hs.py:77-99, ba.py:101-138, classic_nl.py:141-198, alt_ba.py:128-187)
+// uv_io: full-resolution flow (init in, result out).  Ends in a stream
+// synchronisation.
+void run_schedule(of_ctx *c, of_params *P, const FlowPyr &F, F2 &uv_io, of_stats *st) {
+  const int H = uv_io.H, W = uv_io.W, levels = F.levels;
+  const std::vector<Img> &pyr = F.pyr, &gpyr = F.gpyr, &cpyr = F.cpyr, &cgpyr = F.cgpyr;
+  const bool use_guide = F.use_guide;
   F2 uv = uv_io, uvhat;
   if (P->method == OF_METHOD_ALT_BA) {
     uvhat = new_f2(c, H, W);
@@ -1994,12 +2022,33 @@ void compute_flow_dev(of_ctx *c, of_params *P, const Img &images, const Img &gui
   drain_solves(c);
   if (st) {
     float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, t0, t1));
-    st->preprocess_ms += ms;
     for (size_t k = 0; k < lev_ev.size(); ++k) {
       HIPCHK(hipEventElapsedTime(&ms, lev_ev[k].first, lev_ev[k].second));
       st->level_ms[k] = ms;
     }
+  }
+}
+
+// compute_flow (hs.py:49-99, ba.py:57-138, classic_nl.py:89-198, alt_ba.py:81-187)
+// images: device 2nc planes; guide: device gc planes or p == nullptr;
+// uv_io: full-resolution flow (init in, result out).
+void compute_flow_dev(of_ctx *c, of_params *P, const Img &images, const Img &guide, F2 &uv_io, of_stats *st) {
+  check_params(P);
+  hipEvent_t t0 = timing_event(c), t1 = timing_event(c);
+  HIPCHK(hipEventRecord(t0, c->stream));
+  c->prog_t0 = std::chrono::steady_clock::now();
+  FlowPyr F;
+  {
+    // preprocessing (under the lanes' token with OF_PRE_TOKEN)
+    BigPhase pre(c, OF_PRE_TOKEN ? (double)images.H * images.W : 0.0);
+    F = flow_pyramids(c, P, images, guide);
+    HIPCHK(hipEventRecord(t1, c->stream));
+  }
+  run_schedule(c, P, F, uv_io, st);
+  if (st) {
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, t0, t1));
+    st->preprocess_ms += ms;
   }
 }
 
@@ -2037,6 +2086,107 @@ void estimate_dev(of_ctx *c, of_params *P, const void *rgb1, const void *rgb2, b
     float ms = 0;
     HIPCHK(hipEventElapsedTime(&ms, t0, t1));
     st->preprocess_ms += ms;
+  }
+}
+
+// forward-backward check of two device-resident flows (k_fb_check); st_* /
+// er_* dense H x W on the device, st_bw / er_fw / er_bw may be nullptr
+void fb_check(of_ctx *c, const F2 &fw, const F2 &bw, double alpha1, double alpha2, uint8_t *st_fw, float *er_fw,
+              uint8_t *st_bw, float *er_bw) {
+  REQUIRE(fw.H == bw.H && fw.W == bw.W && fw.P == bw.P, OF_EINVAL, "flows of different sizes");
+  c->cur_px = (double)fw.H * fw.W;
+  Grid2 g = grid2(fw.H, fw.W);
+  launch(c, "fb_check", k_fb_check, g.grid, g.block, 0, (const float2 *)fw.p, (const float2 *)bw.p, fw.H, fw.W, fw.P,
+         alpha1, alpha2, st_fw, er_fw, st_bw, er_bw);
+}
+
+// the same levels with the two frames' channel groups exchanged (copies)
+std::vector<Img> swap_frames(of_ctx *c, const std::vector<Img> &pyr) {
+  std::vector<Img> out;
+  for (const Img &m : pyr) {
+    const int nc = m.C / 2;
+    Img s = new_img(c, m.H, m.W, m.C);
+    const size_t half = sizeof(float) * m.ps() * nc;
+    HIPCHK(hipMemcpyAsync(s.p, m.plane(nc), half, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(s.plane(nc), m.p, half, hipMemcpyDeviceToDevice, c->stream));
+    out.push_back(s);
+  }
+  return out;
+}
+
+// Lab guide of `rgb` (interface.py:58-61, 91-141) as estimate_dev builds it
+// for its first frame: the /255 decision from this frame's own maximum.  The
+// gray planes k_rgb_prep writes beside it go to a scratch pair.
+Img lab_guide(of_ctx *c, const float *rgb, const float *other, int H, int W, int C, const Img &gray_out) {
+  Img guide = new_img(c, H, W, C == 3 ? 3 : 1);
+  uint32_t *mm = c->d_mm + 2 * 8;
+  launch(c, "mm_init", k_mm_init, dim3(1), dim3(64), 0, mm, 1);
+  const dim3 mg((unsigned)std::min<long>(((long)H * W * 3 + 255) / 256, 256));
+  if (C == 3) launch(c, "rgb_max", k_rgb_max<float>, mg, dim3(256), 0, rgb, (long)H * W * 3, mm);
+  Grid2 g = grid2(H, W);
+  launch(c, "rgb_prep", k_rgb_prep<float>, g.grid, g.block, 0, rgb, other, H, W, C, gray_out.p, gray_out.P,
+         gray_out.ps(), guide.p, (const uint32_t *)mm);
+  if (C == 3)
+    for (int ch = 0; ch < 3; ++ch) scale_img(c, view(guide, ch, 1), 0.0f, 255.0f, 9 + ch);
+  return guide;
+}
+
+// estimate_flow in both directions with the forward-backward masks.  Gray
+// conversion, the texture split (or scaling) and the image pyramids run once:
+// every one of them treats the two frames' planes alike (per-plane kernels,
+// joint min / max), so the backward pass's pyramids are the forward ones with
+// the planes exchanged.  The colour guide (Lab of each direction's own first
+// frame) and its pyramids are built per direction.
+// rgb1/rgb2: (H, W, C) fp32 frames on the device; st_fw / st_bw: dense H x W
+// device bytes or nullptr
+void estimate_bidir_dev(of_ctx *c, of_params *P, const float *rgb1, const float *rgb2, int H, int W, int C,
+                        F2 &uv_fw, F2 &uv_bw, double alpha1, double alpha2, uint8_t *st_fw, uint8_t *st_bw,
+                        of_stats *sf, of_stats *sb) {
+  REQUIRE(C == 1 || C == 3, OF_EINVAL, "images must be (H,W) or (H,W,3)");
+  check_params(P);
+  hipEvent_t t0 = timing_event(c), t1 = timing_event(c);
+  HIPCHK(hipEventRecord(t0, c->stream));
+  c->prog_t0 = std::chrono::steady_clock::now();
+  const bool guide_mode = P->guide_mode && P->method == OF_METHOD_CLASSIC_NL;
+  FlowPyr F, B;
+  {
+    BigPhase pre(c, OF_PRE_TOKEN ? (double)H * W : 0.0);
+    Img gray = new_img(c, H, W, 2), guide1, guide2;
+    if (guide_mode) {
+      guide1 = lab_guide(c, rgb1, rgb2, H, W, C, gray);
+      guide2 = lab_guide(c, rgb2, rgb1, H, W, C, new_img(c, H, W, 2));
+    } else {
+      uint32_t *mm = c->d_mm + 2 * 8;
+      launch(c, "mm_init", k_mm_init, dim3(1), dim3(64), 0, mm, 1);
+      Grid2 g = grid2(H, W);
+      launch(c, "rgb_prep", k_rgb_prep<float>, g.grid, g.block, 0, rgb1, rgb2, H, W, C, gray.p, gray.P, gray.ps(),
+             (float *)nullptr, (const uint32_t *)mm);
+    }
+    F = flow_pyramids(c, P, gray, guide1);
+    B.levels = F.levels;
+    B.pyr = swap_frames(c, F.pyr);
+    B.gpyr = swap_frames(c, F.gpyr);
+    guide_pyramids(c, P, guide2, B);
+    HIPCHK(hipEventRecord(t1, c->stream));
+  }
+  // both passes start from the caller's alpha and leave the same final one
+  const double alpha0 = P->alpha;
+  const std::vector<size_t> mark = c->arena.mark();
+  run_schedule(c, P, F, uv_fw, sf);
+  if (sf) {
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, t0, t1));
+    sf->preprocess_ms += ms;
+  }
+  c->arena.rewind(mark);  // run_schedule ended in a stream synchronisation
+  P->alpha = alpha0;
+  auto wall1 = std::chrono::steady_clock::now();
+  c->prog_t0 = wall1;
+  run_schedule(c, P, B, uv_bw, sb);
+  if (sb) sb->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall1).count();
+  if (st_fw || st_bw) {
+    if (st_fw) fb_check(c, uv_fw, uv_bw, alpha1, alpha2, st_fw, nullptr, st_bw, nullptr);
+    else fb_check(c, uv_bw, uv_fw, alpha1, alpha2, st_bw, nullptr, nullptr, nullptr);
   }
 }
 
@@ -2448,6 +2598,54 @@ int of_compute_flow(of_ctx *c, of_params *P, const float *images, int H, int W, 
   HIPCHK(hipStreamSynchronize(c->stream));
   if (st)
     st->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+  API_END(c)
+}
+
+int of_fb_consistency(of_ctx *c, const float *fw, const float *bw, int H, int W, double alpha1, double alpha2,
+                      uint8_t *state, float *err) {
+  API_BEGIN(c)
+  REQUIRE(fw && bw && state && H > 0 && W > 0, OF_EINVAL, "bad arguments");
+  REQUIRE(std::isfinite(alpha1) && std::isfinite(alpha2) && alpha1 >= 0 && alpha2 >= 0, OF_EINVAL,
+          "alpha1 and alpha2 must be finite and >= 0");
+  const size_t n = (size_t)H * W;
+  F2 f = upload_f2(c, fw, H, W), b = upload_f2(c, bw, H, W);
+  uint8_t *ds = (uint8_t *)c->arena.alloc(n);
+  float *de = err ? (float *)c->arena.alloc(sizeof(float) * n) : nullptr;
+  fb_check(c, f, b, alpha1, alpha2, ds, de, nullptr, nullptr);
+  HIPCHK(hipMemcpyAsync(state, ds, n, hipMemcpyDeviceToHost, c->stream));
+  if (err) HIPCHK(hipMemcpyAsync(err, de, sizeof(float) * n, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  API_END(c)
+}
+
+int of_estimate_flow_bidir(of_ctx *c, of_params *P, const float *im1, const float *im2, int H, int W, int C,
+                           const float *init_fw, const float *init_bw, float *out_fw, float *out_bw, double alpha1,
+                           double alpha2, uint8_t *state_fw, uint8_t *state_bw, of_stats *sf, of_stats *sb) {
+  API_BEGIN(c)
+  REQUIRE(P && im1 && im2 && out_fw && out_bw && H > 0 && W > 0, OF_EINVAL, "bad arguments");
+  REQUIRE(std::isfinite(alpha1) && std::isfinite(alpha2) && alpha1 >= 0 && alpha2 >= 0, OF_EINVAL,
+          "alpha1 and alpha2 must be finite and >= 0");
+  if (sf) memset(sf, 0, sizeof(*sf));
+  if (sb) memset(sb, 0, sizeof(*sb));
+  auto wall0 = std::chrono::steady_clock::now();
+  const size_t n = (size_t)H * W * C, px = (size_t)H * W;
+  float *d1 = (float *)c->arena.alloc(sizeof(float) * n), *d2 = (float *)c->arena.alloc(sizeof(float) * n);
+  HIPCHK(hipMemcpyAsync(d1, im1, sizeof(float) * n, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(d2, im2, sizeof(float) * n, hipMemcpyHostToDevice, c->stream));
+  F2 uf = init_fw ? upload_f2(c, init_fw, H, W) : new_f2(c, H, W);
+  if (!init_fw) fill_f2(c, uf, 0.0f);
+  F2 ub = init_bw ? upload_f2(c, init_bw, H, W) : new_f2(c, H, W);
+  if (!init_bw) fill_f2(c, ub, 0.0f);
+  uint8_t *dsf = state_fw ? (uint8_t *)c->arena.alloc(px) : nullptr;
+  uint8_t *dsb = state_bw ? (uint8_t *)c->arena.alloc(px) : nullptr;
+  estimate_bidir_dev(c, P, d1, d2, H, W, C, uf, ub, alpha1, alpha2, dsf, dsb, sf, sb);
+  download_f2(c, uf, out_fw);
+  download_f2(c, ub, out_bw);
+  if (state_fw) HIPCHK(hipMemcpyAsync(state_fw, dsf, px, hipMemcpyDeviceToHost, c->stream));
+  if (state_bw) HIPCHK(hipMemcpyAsync(state_bw, dsb, px, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (sf)
+    sf->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
   API_END(c)
 }
 

@@ -465,6 +465,57 @@ __global__ void k_update_occ(const float2 *__restrict__ uv, const float2 *__rest
   }
 }
 
+// ---------------------------------------------------------------------------
+// Forward-backward consistency (Sundaram et al. 2010): follow A at (i, j),
+// sample B bilinearly there and test |A + B|^2 against
+// alpha1 (|A|^2 + |B|^2) + alpha2.  state 0 consistent, 1 inconsistent /
+// occluded, 2 the target leaves the frame (err = +inf).  fp64 from the fp32
+// flows with no contraction, in the order include/optflow.h states, so a
+// numpy float64 restatement gives the same bits.  The comparisons are written
+// so that NaN / Inf targets count as outside.  st / er are dense H x W.
+__device__ __forceinline__ void fb_check_px(const float2 *__restrict__ A, const float2 *__restrict__ B, int i, int j,
+                                            int H, int W, int P, double alpha1, double alpha2,
+                                            uint8_t *__restrict__ st, float *__restrict__ er) {
+  OF_NOCONTRACT
+  const float2 a = A[(size_t)i * P + j];
+  const size_t o = (size_t)i * W + j;
+  const double u = a.x, v = a.y;
+  const double q = (double)j + u, r = (double)i + v;
+  const bool inside = q >= 0.0 && q <= (double)(W - 1) && r >= 0.0 && r <= (double)(H - 1);
+  if (!inside) {
+    st[o] = 2;
+    if (er) er[o] = __builtin_inff();
+    return;
+  }
+  const double qf = floor(q), rf = floor(r);
+  const int j0 = (int)qf, i0 = (int)rf;
+  const double fc = q - qf, fr = r - rf;
+  const int j1 = min(j0 + 1, W - 1), i1 = min(i0 + 1, H - 1);
+  const float2 b00 = B[(size_t)i0 * P + j0], b01 = B[(size_t)i0 * P + j1];
+  const float2 b10 = B[(size_t)i1 * P + j0], b11 = B[(size_t)i1 * P + j1];
+  const double bu = (1.0 - fr) * ((1.0 - fc) * (double)b00.x + fc * (double)b01.x) +
+                    fr * ((1.0 - fc) * (double)b10.x + fc * (double)b11.x);
+  const double bv = (1.0 - fr) * ((1.0 - fc) * (double)b00.y + fc * (double)b01.y) +
+                    fr * ((1.0 - fc) * (double)b10.y + fc * (double)b11.y);
+  const double du = u + bu, dv = v + bv;
+  const double err = du * du + dv * dv;
+  const double thr = alpha1 * ((u * u + v * v) + (bu * bu + bv * bv)) + alpha2;
+  st[o] = err > thr ? 1 : 0;
+  if (er) er[o] = (float)err;
+}
+
+// one thread per pixel; with st_bw != nullptr the same launch also writes the
+// backward mask (the roles of fw and bw exchanged)
+__global__ void k_fb_check(const float2 *__restrict__ fw, const float2 *__restrict__ bw, int H, int W, int P,
+                           double alpha1, double alpha2, uint8_t *__restrict__ st_fw, float *__restrict__ er_fw,
+                           uint8_t *__restrict__ st_bw, float *__restrict__ er_bw) {
+  OF_FOR_PIXELS_XCD(H, W) {
+    if (j >= W) continue;
+    fb_check_px(fw, bw, i, j, H, W, P, alpha1, alpha2, st_fw, er_fw);
+    if (st_bw) fb_check_px(bw, fw, i, j, H, W, P, alpha1, alpha2, st_bw, er_bw);
+  }
+}
+
 // in-place uv += x (HS, hs.py:130-134), optional clip
 __global__ void k_add_update(float2 *__restrict__ uv, const float2 *__restrict__ x, int clip, int H, int W, int P) {
   OF_FOR_PIXELS(H, W) {

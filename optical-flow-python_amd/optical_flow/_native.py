@@ -24,6 +24,7 @@ _fp = C.POINTER(C.c_float)
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int)
 _vp = C.c_void_p
+_u8p = C.POINTER(C.c_uint8)
 
 _SIGS = {
     "of_abi_version": ([], C.c_int),
@@ -42,6 +43,10 @@ _SIGS = {
                           C.POINTER(OfStats)], C.c_int),
     "of_compute_flow": ([_vp, C.POINTER(OfParams), _fp, C.c_int, C.c_int, C.c_int, _fp, C.c_int, _fp, _fp,
                          C.POINTER(OfStats)], C.c_int),
+    "of_fb_consistency": ([_vp, _fp, _fp, C.c_int, C.c_int, C.c_double, C.c_double, _u8p, _fp], C.c_int),
+    "of_estimate_flow_bidir": ([_vp, C.POINTER(OfParams), _fp, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp,
+                                C.c_double, C.c_double, _u8p, _u8p, C.POINTER(OfStats), C.POINTER(OfStats)],
+                               C.c_int),
     "of_compute_flow_base": ([_vp, C.POINTER(OfParams), _fp, C.c_int, C.c_int, C.c_int, _fp, C.c_int,
                               C.c_double, _fp, _fp], C.c_int),
     "of_alt_ba_flow_base": ([_vp, C.POINTER(OfParams), _fp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, _fp,
@@ -220,6 +225,10 @@ def f32(a):
 
 def ptr(a):
     return None if a is None else a.ctypes.data_as(_fp)
+
+
+def u8ptr(a):
+    return None if a is None else a.ctypes.data_as(_u8p)
 
 
 def dptr(a):

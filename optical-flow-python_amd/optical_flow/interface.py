@@ -4,6 +4,7 @@ RGB -> gray (uint8 round trip) and RGB -> Lab (+ per-channel [0,255]
 scaling) run on the GPU inside of_estimate_flow, followed by the whole
 coarse-to-fine schedule; one C call per pair."""
 import ctypes as C
+from collections import namedtuple
 
 import numpy as np
 
@@ -48,6 +49,54 @@ def estimate_flow(im1, im2, method='classic+nl-fast', params=None, gt=None):
     ope.alpha = P.alpha
     ope.last_stats = st.as_dict()
     return nat.interleaved(out)
+
+BidirectionalFlow = namedtuple('BidirectionalFlow', ['forward', 'backward', 'occ_forward', 'occ_backward'])
+
+
+def estimate_flow_bidirectional(im1, im2, method='classic+nl-fast', params=None, alpha1=0.01, alpha2=0.5):
+    """Flow im1 -> im2, flow im2 -> im1 and where each can be trusted.
+
+    Returns BidirectionalFlow(forward, backward, occ_forward, occ_backward):
+    the flows (H, W, 2) float64, equal to estimate_flow(im1, im2, method,
+    params) and estimate_flow(im2, im1, method, params); the masks (H, W)
+    uint8, equal to forward_backward_check(forward, backward, alpha1, alpha2)
+    and the same with the flows exchanged (utils/occlusion.py: FB_CONSISTENT,
+    FB_OCCLUDED, FB_OUT_OF_FRAME).  (H, W) and (H, W, >=3) frames take one C
+    call (of_estimate_flow_bidir) that runs the gray conversion, the
+    structure-texture split and the image pyramids once for both directions."""
+    im1 = np.asarray(im1, dtype=float)
+    im2 = np.asarray(im2, dtype=float)
+    if im1.shape != im2.shape or im1.ndim not in (2, 3):
+        raise ValueError(f"frames must share one (H, W) or (H, W, C) shape, got {im1.shape} / {im2.shape}")
+    H, W = im1.shape[:2]
+    if im1.ndim == 3 and im1.shape[2] < 3:
+        # estimate_flow's compute_flow route (interface.py:47), once per direction
+        from optical_flow.utils.occlusion import forward_backward_check
+        fw = estimate_flow(im1, im2, method, params)
+        bw = estimate_flow(im2, im1, method, params)
+        return BidirectionalFlow(fw, bw, forward_backward_check(fw, bw, alpha1, alpha2),
+                                 forward_backward_check(bw, fw, alpha1, alpha2))
+    ope = load_of_method(method)
+    if params is not None:
+        ope.parse_input_parameter(params)
+    if im1.ndim == 3:
+        a, b, Cc = nat.f32(im1[:, :, :3]), nat.f32(im2[:, :, :3]), 3
+    else:
+        a, b, Cc = nat.f32(im1), nat.f32(im2), 1
+    P = ope.to_params()
+    P.guide_mode = int(ope._METHOD == 'classic_nl' and ope.color_images is not None)
+    out_f = np.empty((2, H, W), dtype=np.float32)
+    out_b = np.empty((2, H, W), dtype=np.float32)
+    occ_f = np.empty((H, W), dtype=np.uint8)
+    occ_b = np.empty((H, W), dtype=np.uint8)
+    st_f, st_b = _abi.OfStats(), _abi.OfStats()
+    ctx = nat.context()
+    fn, flags = progress_printer(ope, None)
+    with ctx.progress(fn, flags):
+        ctx.check(ctx.lib.of_estimate_flow_bidir(ctx.handle, C.byref(P), nat.ptr(a), nat.ptr(b), H, W, Cc, None, None,
+                                                 nat.ptr(out_f), nat.ptr(out_b), float(alpha1), float(alpha2),
+                                                 nat.u8ptr(occ_f), nat.u8ptr(occ_b), C.byref(st_f), C.byref(st_b)))
+    return BidirectionalFlow(nat.interleaved(out_f), nat.interleaved(out_b), occ_f, occ_b)
 
 
 def _as_u8(im):

@@ -17,3 +17,30 @@ def detect_occlusion(uv, images, sigma_d=0.3, sigma_i=20.0):
     ctx.check(ctx.lib.of_detect_occlusion(ctx.handle, nat.ptr(nat.planar(uv)), nat.ptr(nat.planar(images)),
                                           H, W, nc, nat.ptr(out)))
     return out.astype(float)
+
+
+# states of forward_backward_check (of_fb_consistency, include/optflow.h)
+FB_CONSISTENT = 0
+FB_OCCLUDED = 1
+FB_OUT_OF_FRAME = 2
+
+
+def forward_backward_check(fw, bw, alpha1=0.01, alpha2=0.5, return_error=False):
+    """Where the flow `fw` (frame 1 -> 2) can be trusted, given `bw` (frame
+    2 -> 1), both (H, W, 2): follow fw, sample bw there bilinearly and test
+    |fw + bw|^2 <= alpha1 (|fw|^2 + |bw|^2) + alpha2 (Sundaram et al. 2010).
+    Returns the (H, W) uint8 state: FB_CONSISTENT, FB_OCCLUDED (inconsistent
+    or occluded) or FB_OUT_OF_FRAME (the target leaves the frame); with
+    `return_error` also |fw + bw|^2 as (H, W) float32 (+inf out of frame).
+    Swap the arguments for the backward mask."""
+    fw = np.asarray(fw)
+    bw = np.asarray(bw)
+    if fw.ndim != 3 or fw.shape[2] != 2 or fw.shape != bw.shape:
+        raise ValueError(f"flows must both be (H, W, 2), got {fw.shape} / {bw.shape}")
+    H, W = fw.shape[:2]
+    state = np.empty((H, W), dtype=np.uint8)
+    err = np.empty((H, W), dtype=np.float32) if return_error else None
+    ctx = nat.context()
+    ctx.check(ctx.lib.of_fb_consistency(ctx.handle, nat.ptr(nat.planar(fw)), nat.ptr(nat.planar(bw)), H, W,
+                                        float(alpha1), float(alpha2), nat.u8ptr(state), nat.ptr(err)))
+    return (state, err) if return_error else state
