@@ -13,6 +13,9 @@
 #include "kernels.h"
 
 #define PCG_MAX_BLOCKS 512
+static_assert(PCG_MAX_BLOCKS % 256 == 0,
+              "the CG prologue sums PCG_MAX_BLOCKS / 256 partials per lane of a 256-thread block: a remainder would "
+              "be left out");
 // degree of the Chebyshev polynomial preconditioner of the 'backslash'
 // surrogate (k_cgs, k_cg_small): 5 needs 0.70x the iterations of 3 on
 // Classic+NL stage-2 systems (tools/poly_iters.py), and its two extra stencil

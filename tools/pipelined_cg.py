@@ -35,7 +35,7 @@ from optical_flow.utils.synthetic import synth_pair  # noqa: E402
 
 def cheb(m, a, b=2.0):
     """p(B) coefficients of the degree-m Chebyshev residual polynomial on
-    [a, b] (driver.hip cheb_poly)."""
+    [a, b] (host_solve.hip cheb_poly)."""
     from numpy.polynomial import chebyshev as Ch
     from numpy.polynomial import polynomial as Pl
     s, gg = (b + a) / (b - a), -2.0 / (b - a)
