@@ -467,7 +467,11 @@ __global__ __launch_bounds__(256) void k_cg(PcgArgs g, int k, int R, int nbands)
         load_coef(t + 1, cp1);
         RI[(u + 1) & 1] = load_rin(t + 1);
         PO[(u + 2) & 3] = load_po(t + 2);
-        XX[u & 1] = (!FIRST && t >= r0 && t < r1) ? cg_mask1<ODD>(cg_ld4(rx, o8(t)), ok1) : zero4;
+        // (the x load and the stores below are issued at every step, outside
+        // the band with an out-of-range offset: under a branch they lower
+        // the compiler's s_waitcnt vmcnt to the fewest operations of any
+        // path, and the wait then covers loads of this step)
+        XX[u & 1] = FIRST ? zero4 : cg_mask1<ODD>(cg_ld4(rx, t >= r0 && t < r1 ? o8(t) : CG_OOB), ok1);
         // r, z, p of row t
         c0.wlu = cg_from_left(c0.wxu.y);
         c0.wlv = cg_from_left(c0.wxv.y);
@@ -484,14 +488,15 @@ __global__ __launch_bounds__(256) void k_cg(PcgArgs g, int k, int R, int nbands)
         ZZ[u & 1] = z;
         // finish row t-1
         const int o = t - 1;
+        const cg_f4 pm1 = PP[(u + 3) & 3], rm1 = RR[(u + 1) & 1], zm1 = ZZ[(u + 1) & 1];
+        unsigned so = o >= r0 ? soff8 + (unsigned)o * rowb8 : CG_OOB;
+        asm("" : "+v"(so));  // keeps the select (else the stores go back under the branch)
+        cg_st4(rro, so, rm1);
+        cg_st4(rpn, so, pm1);
+        cg_st4(rx, so, FIRST ? zero4 : XX[(u + 1) & 1] + alpha * PO[(u + 3) & 3]);
         if (o >= r0) {
-          const cg_f4 pm1 = PP[(u + 3) & 3], rm1 = RR[(u + 1) & 1], zm1 = ZZ[(u + 1) & 1];
           const cg_f4 q = cg_apply(PP[(u + 2) & 3], pm1, p, cm1, cm2.wyu, cm2.wyv);
           const cg_f4 mq = cg_minv(MI[(u + 1) & 1], q);
-          const unsigned so = soff8 + (unsigned)o * rowb8;
-          cg_st4(rro, so, rm1);
-          cg_st4(rpn, so, pm1);
-          cg_st4(rx, so, FIRST ? zero4 : XX[(u + 1) & 1] + alpha * PO[(u + 3) & 3]);
           // per-lane fp32 dots over the two pixels (halo lanes / padding masked)
           cg_f4 qm = q, rm = rm1;  // select, not multiply: halo lanes may hold inf/nan
           if (!dm0) { qm.x = 0.f; qm.y = 0.f; rm.x = 0.f; rm.y = 0.f; }
@@ -1151,8 +1156,18 @@ template __global__ void k_cg_reg<0, false>(CgSmallArgs);
 #ifndef CGS_PF
 #define CGS_PF 2
 #endif
+// The distance holds only while every row step issues the same memory
+// operations: the compiler sizes each s_waitcnt vmcnt for the fewest
+// operations any path can have put behind the awaited load.  With wave 2's x
+// load and stores under branches it waited with vmcnt(1), i.e. for the p_old
+// load of the same step (distance 0, whatever CGS_PF2 said: the round-2
+// sweep of 2..4 was flat for that reason).  Unconditional (load_x, so8) the
+// wait is vmcnt(5) at distance 1, vmcnt(9) at 2.  Timed bench, 5 alternating
+// runs each on one box, the same flow bitwise: conditional 51.01 +- 0.04,
+// then CGS_PF2 1 / 2 / 3: 52.55 +- 0.14 / 53.02 +- 0.08 / 52.78 +- 0.04
+// pairs/s (profiles/r7_cgs_waits/).
 #ifndef CGS_PF2
-#define CGS_PF2 1
+#define CGS_PF2 2
 #endif
 #define CGS_POW2(n) ((n) <= 1 ? 1 : (n) <= 2 ? 2 : (n) <= 4 ? 4 : 8)
 #define CGS_SGN CGS_POW2(CGS_PF + 2)
@@ -1294,8 +1309,13 @@ __global__ __launch_bounds__(256) void k_cgs(PcgArgs g, int k, int R, int nbands
   // x_lo = 0 in the launch after a residual replacement (xz, known after
   // the prologue; the preamble's x rows are then dropped)
   bool xz = false;
+  // (always issued: outside the band, and after xz, from an out-of-range
+  // offset that returns 0 without memory traffic.  A branch around the load
+  // makes the count of memory operations behind an earlier load depend on
+  // the path, and the wait before that load's use then covers this step's)
   auto load_x = [&](int t) {
-    return (!FIRST && !xz && t >= r0 && t < r1) ? cg_mask1<ODD>(cg_ld4(rx, o8(t)), ok1) : cg_f4{0.f, 0.f, 0.f, 0.f};
+    if (FIRST) return cg_f4{0.f, 0.f, 0.f, 0.f};
+    return cg_mask1<ODD>(cg_ld4(rx, !xz && t >= r0 && t < r1 ? o8(t) : CG_OOB), ok1);
   };
   const bool dm0 = out_lane && ok0, dm1 = out_lane && ok1;
   auto mdot = [&](cg_f4 a, cg_f4 b) {
@@ -1346,8 +1366,17 @@ __global__ __launch_bounds__(256) void k_cgs(PcgArgs g, int k, int R, int nbands
 
   double acc[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
   CgRec QA[2];  // CGS_W0REG: wave 0's records of rows n - 2, n - 1 (by R2)
-  // row o inside the band (stores and dot products only there)
+  // row o inside the band (stores and dot products only there); so8: the
+  // store offset of row o, out of range (the store is dropped) outside the
+  // band, so that every row step issues the same memory operations
   auto inband = [&](int o) { return o >= r0 && o < r1; };
+  // (the empty asm keeps the select: without it the compiler threads the
+  // stores back into the two arms of the inband branch below them)
+  auto so8 = [&](int o) {
+    unsigned ro = inband(o) ? orow(o) * rowb8 : CG_ROW_OOB;
+    asm("" : "+s"(ro));
+    return soff8 + ro;
+  };
   if (live) {
     if (role == 0) {
       QA[0] = put_rec(ns - 2, SGp[0]);  // ring slots of rows ns - 2, ns - 1 at u = 0
@@ -1406,8 +1435,8 @@ __global__ __launch_bounds__(256) void k_cgs(PcgArgs g, int k, int R, int nbands
         const cg_f4 y = cgr_minv(q1, r);
         s_y[(n - 1) & 7][lane] = make_float4(y.x, y.y, y.z, y.w);
         const int o = n - 1;
+        cg_st4(rro, so8(o), r);
         if (inband(o)) {
-          cg_st4(rro, soff8 + orow(o) * rowb8, r);
           acc[4] += (double)mdot(r, r);
           acc[3] += (double)(c0 * mdot(r, y));
         }
@@ -1477,12 +1506,10 @@ __global__ __launch_bounds__(256) void k_cgs(PcgArgs g, int k, int R, int nbands
           if (!(rv && ok1)) { p.z = 0.f; p.w = 0.f; }
           PP[R4(-8)] = p;
           ZZ[R2(-8)] = z;
-          if (inband(o)) {
-            const unsigned so = soff8 + orow(o) * rowb8;
-            cg_st4(rpn, so, p);
-            cg_st4(rx, so, FIRST ? zero4 : XI[RW2(-8)] + alpha * PO2[RW2(-8)]);
-            acc[3] += (double)mdot(yr, ng);
-          }
+          const unsigned so = so8(o);
+          cg_st4(rpn, so, p);
+          cg_st4(rx, so, FIRST ? zero4 : XI[RW2(-8)] + alpha * PO2[RW2(-8)]);
+          if (inband(o)) acc[3] += (double)mdot(yr, ng);
         }
         // E) row n-9: q = A p, y_q = D^-1 q
         {
