@@ -303,6 +303,89 @@ int of_estimate_flow_bidir(of_ctx *ctx, of_params *params, const float *im1, con
                            float *out_fw, float *out_bw, double alpha1, double alpha2,
                            uint8_t *state_fw, uint8_t *state_bw, of_stats *stats_fw, of_stats *stats_bw);
 
+/*
+ * Using a flow on an image.  Common definitions, all in double from the fp32
+ * inputs, no fma contraction, in exactly this order (a numpy float64
+ * restatement gives the same bits); images are H x W x C interleaved:
+ *   bil(A, r, q), r and q finite: the clamped bilinear sample of a plane
+ *     qc = min(max(q, 0), W-1); j0 = floor(qc); fc = qc - j0; j1 = min(j0+1, W-1)
+ *     rc, i0, fr, i1 the same with rows and H
+ *     (1-fr)*((1-fc)*A[i0][j0] + fc*A[i0][j1]) + fr*((1-fc)*A[i1][j0] + fc*A[i1][j1])
+ *   inside(r, q) = q >= 0 && q <= W-1 && r >= 0 && r <= H-1
+ *   near(x, n)   = min(max(floor(x + 0.5), 0), n-1)
+ *
+ * of_warp_image: out(i, j, c) = (float)bil(im_c, i + v, j + u) with
+ * (u, v) = uv(i, j) (planar 2 x H x W: u along columns, v along rows);
+ * valid (H x W bytes or NULL) = inside(i + v, j + u).  A flow with a NaN or
+ * Inf component gives valid 0 and out 0.  C is 1..4.
+ */
+int of_warp_image(of_ctx *ctx, const float *im, int H, int W, int C, const float *uv, float *out, uint8_t *valid);
+
+/*
+ * Occlusion-aware frame interpolation (Baker et al. 2011, sec. 3.3.2): the
+ * frames at times t[0..n) strictly between im1 (time 0) and im2 (time 1) from
+ * the flows F = fw (1 -> 2) and B = bw (2 -> 1), planar 2 x H x W.  Sf / Sb are
+ * the states of of_fb_consistency(fw, bw) / (bw, fw) with alpha1, alpha2,
+ * computed once per call.  Per t, with omt = 1.0 - t:
+ *
+ * 1. Splat.  Every source pixel (i, j), s = i*W + j, of frame f = 0
+ *    ((u, v) = F[i][j], motion (a, b) = (u, v), tau = t) and of frame f = 1
+ *    ((u, v) = B[i][j], (a, b) = (-u, -v), tau = omt) whose u and v are finite:
+ *      q = j + tau*u; r = i + tau*v; jf = floor(q); i_f = floor(r)
+ *      for di, dj in {0,1}^2: target (ti, tj) = (i_f + di, jf + dj), skipped
+ *        when outside the frame (tested in double) or when its bilinear weight
+ *        is zero (dj == 1 && q == jf, or di == 1 && r == i_f)
+ *      cost = sum over c ascending of
+ *             |bil(I1_c, ti - t*b, tj - t*a) - bil(I2_c, ti + omt*b, tj + omt*a)|
+ *      K = (uint64)bits((float)cost) << 32 | f << 31 | s
+ *    and the smallest K per target wins (a 64-bit atomic minimum: a
+ *    non-negative float's bits order like its value, so the cheapest motion
+ *    at the target wins, ties go to frame 1's flow, then to the lowest source
+ *    index, whatever the order of arrival).  H*W >= 2^31: OF_ENOTSUP.
+ * 2. Resolve.  A target nothing reached is a hole; otherwise its motion is
+ *    ut = f ? -B[s] : F[s] (fp32, exact).
+ * 3. Fill.  Jacobi passes: a hole with at least one non-hole among its 8
+ *    neighbours as of the previous pass takes, per component, the double sum
+ *    of those neighbours (row-major order) divided by their count, rounded to
+ *    fp32, and is a non-hole from the next pass on; repeated until no hole is
+ *    left.  A pass that fills nothing means no pixel has a motion: then
+ *    ut = 0 everywhere and every pixel renders as the plain blend, info 3.
+ * 4. Render pixel (i, j), (a, b) = ut:
+ *      p1 = (i - t*b, j - t*a); p2 = (i + omt*b, j + omt*a)
+ *      in1 = inside(p1); in2 = inside(p2)
+ *      o1 = in1 && Sf[near(p1)] == 1   (frame 1's point is not visible in frame 2)
+ *      o2 = in2 && Sb[near(p2)] == 1
+ *      w1 = in1 && !o2;  w2 = in2 && !o1
+ *      s1 = bil(I1_c, p1); s2 = bil(I2_c, p2)
+ *      w1 && w2: omt*s1 + t*s2, info 0;  w1 only: s1, info 1;
+ *      w2 only: s2, info 2;  neither: omt*s1 + t*s2, info 3
+ *      out = (float) of that; info |= 4 where ut came from the hole filling
+ *   out      : n x H x W x C
+ *   out_ut   : n x 2 x H x W planar, the motion at time t, or NULL
+ *   out_info : n x H x W bytes, or NULL
+ * C is 1..4, n >= 1, every t[k] strictly inside (0, 1), alpha1 / alpha2 as
+ * for of_fb_consistency; anything else: OF_EINVAL.
+ * Known limitation: a surface that both frames see but that is hidden at time
+ * t offers its motion at the same cost as the surface hiding it (the cost
+ * compares the two frames only), so a thin occluder crossing in front of it
+ * between the frames can lose its pixels at time t.
+ */
+int of_interp_frames(of_ctx *ctx, const float *im1, const float *im2, int H, int W, int C,
+                     const float *fw, const float *bw, double alpha1, double alpha2,
+                     int n, const double *t, float *out, float *out_ut, uint8_t *out_info);
+
+/*
+ * of_estimate_flow_bidir followed by of_interp_frames on the device-resident
+ * frames, flows and states, one call: the flows never visit the host in
+ * between, and out / out_info equal (bitwise) those of the two calls.  C is
+ * 1 or 3 as for of_estimate_flow; out_fw / out_bw (planar 2 x H x W),
+ * out_info and the stats (as for of_estimate_flow_bidir) may be NULL.
+ */
+int of_estimate_interp(of_ctx *ctx, of_params *params, const float *im1, const float *im2,
+                       int H, int W, int C, double alpha1, double alpha2, int n, const double *t,
+                       float *out, float *out_fw, float *out_bw, uint8_t *out_info,
+                       of_stats *stats_fw, of_stats *stats_bw);
+
 /* compute_flow_base() for one pyramid level with the given alpha (one call =
  * all warping iterations of the level; hs.py:109-142, ba.py:143-206,
  * classic_nl.py:200-277).  uv_in / out_uv planar 2 x H x W. */

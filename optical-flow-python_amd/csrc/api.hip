@@ -360,6 +360,68 @@ int of_estimate_flow_bidir(of_ctx *c, of_params *P, const float *im1, const floa
   API_END(c)
 }
 
+int of_warp_image(of_ctx *c, const float *im, int H, int W, int C, const float *uv, float *out, uint8_t *valid) {
+  API_BEGIN(c)
+  REQUIRE(im && uv && out && H > 0 && W > 0, OF_EINVAL, "bad arguments");
+  REQUIRE(C >= 1 && C <= OF_MAX_NC, OF_EINVAL, "images must have 1 to 4 channels");
+  const size_t px = (size_t)H * W;
+  float *dim = (float *)c->arena.alloc(sizeof(float) * px * C);
+  HIPCHK(hipMemcpyAsync(dim, im, sizeof(float) * px * C, hipMemcpyHostToDevice, c->stream));
+  F2 f = upload_f2(c, uv, H, W);
+  float *dout = (float *)c->arena.alloc(sizeof(float) * px * C);
+  uint8_t *dv = valid ? (uint8_t *)c->arena.alloc(px) : nullptr;
+  c->cur_px = (double)px;
+  Grid2 g = grid2(H, W);
+  launch(c, "warp_image", k_warp_image, g.grid, g.block, 0, (const float *)dim, C, (const float2 *)f.p, H, W, f.P,
+         dout, dv);
+  HIPCHK(hipMemcpyAsync(out, dout, sizeof(float) * px * C, hipMemcpyDeviceToHost, c->stream));
+  if (valid) HIPCHK(hipMemcpyAsync(valid, dv, px, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  API_END(c)
+}
+
+int of_interp_frames(of_ctx *c, const float *im1, const float *im2, int H, int W, int C, const float *fw,
+                     const float *bw, double alpha1, double alpha2, int n, const double *t, float *out,
+                     float *out_ut, uint8_t *out_info) {
+  API_BEGIN(c)
+  REQUIRE(im1 && im2 && fw && bw && out && H > 0 && W > 0, OF_EINVAL, "bad arguments");
+  REQUIRE(C >= 1 && C <= OF_MAX_NC, OF_EINVAL, "images must have 1 to 4 channels");
+  check_interp_args(H, W, alpha1, alpha2, n, t);
+  const size_t px = (size_t)H * W;
+  float *d1, *d2;
+  upload_frames(c, im1, im2, px * C, &d1, &d2);
+  F2 f = upload_f2(c, fw, H, W), b = upload_f2(c, bw, H, W);
+  uint8_t *dsf = (uint8_t *)c->arena.alloc(px), *dsb = (uint8_t *)c->arena.alloc(px);
+  fb_check(c, f, b, alpha1, alpha2, dsf, nullptr, dsb, nullptr);
+  interp_frames_dev(c, d1, d2, H, W, C, f, b, dsf, dsb, n, t, out, out_ut, out_info);
+  HIPCHK(hipStreamSynchronize(c->stream));
+  API_END(c)
+}
+
+int of_estimate_interp(of_ctx *c, of_params *P, const float *im1, const float *im2, int H, int W, int C,
+                       double alpha1, double alpha2, int n, const double *t, float *out, float *out_fw,
+                       float *out_bw, uint8_t *out_info, of_stats *sf, of_stats *sb) {
+  API_BEGIN(c)
+  REQUIRE(P && im1 && im2 && out && H > 0 && W > 0, OF_EINVAL, "bad arguments");
+  REQUIRE(C == 1 || C == 3, OF_EINVAL, "images must be (H,W) or (H,W,3)");
+  check_interp_args(H, W, alpha1, alpha2, n, t);
+  if (sf) memset(sf, 0, sizeof(*sf));
+  if (sb) memset(sb, 0, sizeof(*sb));
+  const WallClock wall;
+  const size_t px = (size_t)H * W;
+  float *d1, *d2;
+  upload_frames(c, im1, im2, px * C, &d1, &d2);
+  F2 uf = init_flow(c, nullptr, H, W), ub = init_flow(c, nullptr, H, W);
+  uint8_t *dsf = (uint8_t *)c->arena.alloc(px), *dsb = (uint8_t *)c->arena.alloc(px);
+  estimate_bidir_dev(c, P, d1, d2, H, W, C, uf, ub, alpha1, alpha2, dsf, dsb, sf, sb);
+  interp_frames_dev(c, d1, d2, H, W, C, uf, ub, dsf, dsb, n, t, out, nullptr, out_info);
+  if (out_fw) download_f2(c, uf, out_fw);
+  if (out_bw) download_f2(c, ub, out_bw);
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (sf) sf->total_ms = wall.ms();
+  API_END(c)
+}
+
 int of_compute_flow_base(of_ctx *c, of_params *P, const float *images, int H, int W, int nc, const float *guide,
                          int gc, double alpha, const float *uv_in, float *out_uv) {
   API_BEGIN(c)

@@ -652,6 +652,78 @@ void estimate_bidir_dev(of_ctx *c, of_params *P, const float *rgb1, const float 
   }
 }
 
+// a device counter's value, after everything queued on the stream so far
+unsigned read_count(of_ctx *c, const unsigned *d) {
+  unsigned h = 0;
+  HIPCHK(hipMemcpyAsync(&h, d, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return h;
+}
+
+// Frames at times t[0..n) between two device-resident frames (dense
+// H x W x C) from their flows and forward-backward states (k_interp_*): per
+// t one splat, one resolve, as many fill passes as the holes need and one
+// render; the frames, flows and states are shared.  out (n x H x W x C),
+// out_ut (n x 2 x H x W planar or nullptr) and out_info (n x H x W or
+// nullptr) are host buffers.
+void interp_frames_dev(of_ctx *c, const float *d1, const float *d2, int H, int W, int C, const F2 &fw, const F2 &bw,
+                       const uint8_t *sf, const uint8_t *sb, int n, const double *t, float *out, float *out_ut,
+                       uint8_t *out_info) {
+  const size_t px = (size_t)H * W;
+  unsigned long long *key = (unsigned long long *)c->arena.alloc(sizeof(unsigned long long) * px);
+  F2 ut[2] = {new_f2(c, H, W), new_f2(c, H, W)};
+  uint8_t *hole[2] = {(uint8_t *)c->arena.alloc(px), (uint8_t *)c->arena.alloc(px)};
+  unsigned *cnt = (unsigned *)c->arena.alloc(sizeof(unsigned));
+  float *dout = (float *)c->arena.alloc(sizeof(float) * px * C);
+  float *dut = out_ut ? (float *)c->arena.alloc(sizeof(float) * 2 * px) : nullptr;
+  uint8_t *dinfo = (uint8_t *)c->arena.alloc(px);
+  c->cur_px = (double)px;
+  const Grid2 g = grid2(H, W);
+  for (int k = 0; k < n; ++k) {
+    const double tk = t[k], omt = 1.0 - tk;
+    HIPCHK(hipMemsetAsync(key, 0xff, sizeof(unsigned long long) * px, c->stream));
+    HIPCHK(hipMemsetAsync(cnt, 0, sizeof(unsigned), c->stream));
+    launch(c, "interp_splat", k_interp_splat, gz(g, 2), g.block, 0, d1, d2, C, (const float2 *)fw.p,
+           (const float2 *)bw.p, H, W, fw.P, tk, omt, key);
+    launch(c, "interp_resolve", k_interp_resolve, g.grid, g.block, 0, (const unsigned long long *)key,
+           (const float2 *)fw.p, (const float2 *)bw.p, H, W, fw.P, ut[0].p, hole[0], cnt);
+    int cur = 0;
+    // Jacobi passes until no hole is left; a pass that fills nothing means no
+    // pixel has a motion at all: zero motion everywhere
+    for (unsigned holes = read_count(c, cnt); holes > 0;) {
+      HIPCHK(hipMemsetAsync(cnt, 0, sizeof(unsigned), c->stream));
+      launch(c, "interp_fill", k_interp_fill, g.grid, g.block, 0, (const float2 *)ut[cur].p,
+             (const uint8_t *)hole[cur], ut[cur ^ 1].p, hole[cur ^ 1], H, W, fw.P, cnt);
+      cur ^= 1;
+      const unsigned left = read_count(c, cnt);
+      if (left == holes) {
+        HIPCHK(hipMemsetAsync(ut[cur].p, 0, sizeof(float2) * (size_t)H * fw.P, c->stream));
+        break;
+      }
+      holes = left;
+    }
+    launch(c, "interp_render", k_interp_render, g.grid, g.block, 0, d1, d2, C, (const float2 *)ut[cur].p,
+           (const uint8_t *)hole[cur], sf, sb, H, W, fw.P, tk, omt, dout, dinfo);
+    HIPCHK(hipMemcpyAsync(out + (size_t)k * px * C, dout, sizeof(float) * px * C, hipMemcpyDeviceToHost, c->stream));
+    if (out_ut) {
+      f2_to_dense(c, ut[cur], dut);
+      HIPCHK(hipMemcpyAsync(out_ut + (size_t)k * 2 * px, dut, sizeof(float) * 2 * px, hipMemcpyDeviceToHost,
+                            c->stream));
+    }
+    if (out_info) HIPCHK(hipMemcpyAsync(out_info + (size_t)k * px, dinfo, px, hipMemcpyDeviceToHost, c->stream));
+  }
+}
+
+// the arguments the interpolation entries share (before anything is uploaded)
+void check_interp_args(int H, int W, double alpha1, double alpha2, int n, const double *t) {
+  REQUIRE((size_t)H * W < ((size_t)1 << 31), OF_ENOTSUP,
+          "frame interpolation takes H * W < 2^31 (the splat key holds a 31-bit source index)");
+  REQUIRE(std::isfinite(alpha1) && std::isfinite(alpha2) && alpha1 >= 0 && alpha2 >= 0, OF_EINVAL,
+          "alpha1 and alpha2 must be finite and >= 0");
+  REQUIRE(n >= 1 && t, OF_EINVAL, "at least one time t");
+  for (int k = 0; k < n; ++k) REQUIRE(t[k] > 0.0 && t[k] < 1.0, OF_EINVAL, "every t must lie strictly inside (0, 1)");
+}
+
 // estimate_flow on a device-resident slot, on ctx c's stream (synchronous)
 void run_slot(of_ctx *c, const Slot &s, of_params *P, of_stats *st) {
   if (st) memset(st, 0, sizeof(*st));

@@ -5,7 +5,9 @@ compute_flow() API and method registry; the coarse-to-fine IRLS hot path runs
 as hand-written HIP kernels for gfx950 in liboptflow.so (include/optflow.h).
 """
 from optical_flow.interface import (estimate_flow, estimate_flow_batch, PairStream, estimate_flow_bidirectional,
-                                    BidirectionalFlow)
+                                    BidirectionalFlow, interpolate_frames, INTERP_BLEND, INTERP_FRAME1_ONLY,
+                                    INTERP_FRAME2_ONLY, INTERP_NEITHER, INTERP_FILLED)
+from optical_flow.utils.warping import warp_image
 from optical_flow.utils.occlusion import forward_backward_check, FB_CONSISTENT, FB_OCCLUDED, FB_OUT_OF_FRAME
 from optical_flow.io.flo_io import read_flo, write_flo
 from optical_flow.viz.flow_color import flow_to_color
@@ -15,4 +17,5 @@ from optical_flow.methods.config import load_of_method
 
 __all__ = ['estimate_flow', 'estimate_flow_batch', 'PairStream', 'read_flo', 'write_flo', 'flow_to_color', 'plot_flow', 'flow_angular_error',
            'load_of_method', 'estimate_flow_bidirectional', 'BidirectionalFlow', 'forward_backward_check',
-           'FB_CONSISTENT', 'FB_OCCLUDED', 'FB_OUT_OF_FRAME']
+           'FB_CONSISTENT', 'FB_OCCLUDED', 'FB_OUT_OF_FRAME', 'interpolate_frames', 'warp_image', 'INTERP_BLEND',
+           'INTERP_FRAME1_ONLY', 'INTERP_FRAME2_ONLY', 'INTERP_NEITHER', 'INTERP_FILLED']

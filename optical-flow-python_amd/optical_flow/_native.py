@@ -47,6 +47,11 @@ _SIGS = {
     "of_estimate_flow_bidir": ([_vp, C.POINTER(OfParams), _fp, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp,
                                 C.c_double, C.c_double, _u8p, _u8p, C.POINTER(OfStats), C.POINTER(OfStats)],
                                C.c_int),
+    "of_warp_image": ([_vp, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp, _u8p], C.c_int),
+    "of_interp_frames": ([_vp, _fp, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp, C.c_double, C.c_double, C.c_int, _dp,
+                          _fp, _fp, _u8p], C.c_int),
+    "of_estimate_interp": ([_vp, C.POINTER(OfParams), _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double,
+                            C.c_int, _dp, _fp, _fp, _fp, _u8p, C.POINTER(OfStats), C.POINTER(OfStats)], C.c_int),
     "of_compute_flow_base": ([_vp, C.POINTER(OfParams), _fp, C.c_int, C.c_int, C.c_int, _fp, C.c_int,
                               C.c_double, _fp, _fp], C.c_int),
     "of_alt_ba_flow_base": ([_vp, C.POINTER(OfParams), _fp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, _fp,

@@ -99,6 +99,88 @@ def estimate_flow_bidirectional(im1, im2, method='classic+nl-fast', params=None,
     return BidirectionalFlow(nat.interleaved(out_f), nat.interleaved(out_b), occ_f, occ_b)
 
 
+# info byte of interpolate_frames (of_interp_frames, include/optflow.h)
+INTERP_BLEND = 0
+INTERP_FRAME1_ONLY = 1
+INTERP_FRAME2_ONLY = 2
+INTERP_NEITHER = 3
+INTERP_FILLED = 4
+
+
+def interpolate_frames(im1, im2, t=0.5, method='classic+nl-fast', params=None, flows=None, alpha1=0.01, alpha2=0.5,
+                       return_info=False):
+    """The frame(s) at time(s) `t`, strictly between im1 (t = 0) and im2
+    (t = 1), by occlusion-aware interpolation along the flows of both
+    directions (Baker et al. 2011 sec. 3.3.2; include/optflow.h states the
+    arithmetic).  A scalar `t` gives one float64 frame of im1's shape, a
+    sequence a list of them.
+
+    `flows` = (forward, backward), each (H, W, 2), or a BidirectionalFlow
+    interpolates along flows you already have (of_interp_frames; frames of 1
+    to 4 channels).  Without it the flows are estimated with `method` /
+    `params` as estimate_flow_bidirectional does, and (H, W) and (H, W, 3)
+    frames take one C call (of_estimate_interp) that keeps the frames, flows
+    and forward-backward masks on the device; the frames equal those of
+    estimate_flow_bidirectional followed by interpolate_frames(flows=...).
+    alpha1 / alpha2 are the thresholds of forward_backward_check.
+
+    With `return_info` the result is (frames, ut, info): per frame also the
+    motion at time t, (H, W, 2) float64, and the (H, W) uint8 info byte
+    (INTERP_BLEND, INTERP_FRAME1_ONLY, INTERP_FRAME2_ONLY or INTERP_NEITHER,
+    plus INTERP_FILLED where the motion came from hole filling); estimated
+    flows then make the round trip of estimate_flow_bidirectional."""
+    im1 = np.asarray(im1, dtype=float)
+    im2 = np.asarray(im2, dtype=float)
+    if im1.shape != im2.shape or im1.ndim not in (2, 3) or im1.size == 0:
+        raise ValueError(f"frames must share one non-empty (H, W) or (H, W, C) shape, got {im1.shape} / {im2.shape}")
+    H, W = im1.shape[:2]
+    Cc = im1.shape[2] if im1.ndim == 3 else 1
+    if not 1 <= Cc <= 4:
+        raise ValueError(f"frames must have 1 to 4 channels, got {Cc}")
+    scalar = np.ndim(t) == 0
+    ts = np.atleast_1d(np.asarray(t, dtype=np.float64))
+    if ts.ndim != 1 or ts.size == 0 or not np.all(np.isfinite(ts) & (ts > 0) & (ts < 1)):
+        raise ValueError(f"t must be one or more times strictly inside (0, 1), got {t!r}")
+    ts = np.ascontiguousarray(ts)
+    n = ts.size
+    if flows is not None:
+        fw, bw = (flows.forward, flows.backward) if isinstance(flows, BidirectionalFlow) else flows
+        fw, bw = np.asarray(fw), np.asarray(bw)
+        if fw.shape != (H, W, 2) or bw.shape != (H, W, 2):
+            raise ValueError(f"flows must both be ({H}, {W}, 2), got {fw.shape} / {bw.shape}")
+    elif return_info or (im1.ndim == 3 and Cc != 3):
+        r = estimate_flow_bidirectional(im1, im2, method, params, alpha1, alpha2)
+        fw, bw = r.forward, r.backward
+    a, b = nat.f32(im1), nat.f32(im2)
+    out = np.empty((n, H, W, Cc), dtype=np.float32)
+    ut = np.empty((n, 2, H, W), dtype=np.float32) if return_info else None
+    info = np.empty((n, H, W), dtype=np.uint8) if return_info else None
+    if flows is not None or return_info or (im1.ndim == 3 and Cc != 3):
+        ctx = nat.context()
+        ctx.check(ctx.lib.of_interp_frames(ctx.handle, nat.ptr(a), nat.ptr(b), H, W, Cc, nat.ptr(nat.planar(fw)),
+                                           nat.ptr(nat.planar(bw)), float(alpha1), float(alpha2), n, nat.dptr(ts),
+                                           nat.ptr(out), nat.ptr(ut), nat.u8ptr(info)))
+    else:
+        ope = load_of_method(method)
+        if params is not None:
+            ope.parse_input_parameter(params)
+        P = ope.to_params()
+        P.guide_mode = int(ope._METHOD == 'classic_nl' and ope.color_images is not None)
+        st_f, st_b = _abi.OfStats(), _abi.OfStats()
+        ctx = nat.context()
+        fn, flags = progress_printer(ope, None)
+        with ctx.progress(fn, flags):
+            ctx.check(ctx.lib.of_estimate_interp(ctx.handle, C.byref(P), nat.ptr(a), nat.ptr(b), H, W, Cc,
+                                                 float(alpha1), float(alpha2), n, nat.dptr(ts), nat.ptr(out), None,
+                                                 None, None, C.byref(st_f), C.byref(st_b)))
+    frames = [out[k].reshape(im1.shape).astype(np.float64) for k in range(n)]
+    if not return_info:
+        return frames[0] if scalar else frames
+    uts = [nat.interleaved(ut[k]) for k in range(n)]
+    infos = [info[k] for k in range(n)]
+    return (frames[0], uts[0], infos[0]) if scalar else (frames, uts, infos)
+
+
 def _as_u8(im):
     a = np.asarray(im)
     if a.dtype == np.uint8:
