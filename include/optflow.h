@@ -256,6 +256,53 @@ int of_compute_flow(of_ctx *ctx, of_params *params, const float *images, int H, 
                     const float *guide, int gc, const float *init_uv, float *out_uv, of_stats *stats);
 
 /*
+ * Per-pixel data-term weights (validity and confidence masks).  A weight
+ * plane w is H x W float32, dense, every value finite and >= 0 (not limited
+ * to <= 1); anything else: OF_EINVAL, checked on the host before any launch.
+ * Where w is 0 the data term is gone and the smoothness term inpaints the
+ * flow from its surroundings.  At pixel (i, j) of a level the assembled
+ * system (of_flow_operator's planes) uses
+ *   psi_w = psi * w[i][j]
+ * in place of psi, the pixel's data weight: one fp32 product applied to the
+ * finished psi (after the channel mean and the GNC blend of the quadratic and
+ * the robust penalty), never contracted into an fma, in
+ *   a_uu = psi_w*<Ix Ix> + (edge weights)      b_u = -(smoothness) - psi_w*<It Ix>
+ *   a_uv = psi_w*<Ix Iy>                       b_v = -(smoothness) - psi_w*<It Iy>
+ *   a_vv = psi_w*<Iy Iy> + (edge weights)
+ * The smoothness weights, the clip and update, the occlusion detection and
+ * both median filters do not see w.  The coarse levels use the weight's own
+ * pyramid: the one-plane image w goes through the Gaussian and the bilinear
+ * resize the frames get, with the levels and spacing of the image pyramid it
+ * accompanies and again with those of the GNC pyramid.  Both steps are convex
+ * combinations, so every level stays >= 0.
+ * A NULL weight is the unweighted entry, bitwise (the same kernels).  A weight
+ * with params->filters.general or with AltBA (classic-c-a): OF_ENOTSUP.  The
+ * batch and stream entries (of_pairs_*), of_estimate_flow_bidir and
+ * of_estimate_interp take no weight.
+ * Known limitation: the content of a masked region still enters the global
+ * minimum and maximum of the structure-texture split / scale_image, and the
+ * blurred coarse frames around it; the weight pyramid only down-weights the
+ * coarse pixels it pollutes.  Fill masked pixels with plausible values (their
+ * surroundings, the other frame) rather than with extremes.
+ *
+ * Each entry is its unweighted sibling with `weight` added.
+ * of_compute_flow_base_weighted uses the weight as given, for that one level;
+ * of_flow_operator_weighted (a stage entry for the parity tests) likewise.
+ */
+int of_estimate_flow_weighted(of_ctx *ctx, of_params *params, const float *im1, const float *im2,
+                              int H, int W, int C, const float *init_uv, const float *weight,
+                              float *out_uv, of_stats *stats);
+int of_compute_flow_weighted(of_ctx *ctx, of_params *params, const float *images, int H, int W, int nc,
+                             const float *guide, int gc, const float *init_uv, const float *weight,
+                             float *out_uv, of_stats *stats);
+int of_compute_flow_base_weighted(of_ctx *ctx, of_params *params, const float *images, int H, int W, int nc,
+                                  const float *guide, int gc, double alpha, const float *uv_in,
+                                  const float *weight, float *out_uv);
+int of_flow_operator_weighted(of_ctx *ctx, const of_params *params, double alpha, const float *uv,
+                              const float *duv, const float *weight, const float *It, const float *Ix,
+                              const float *Iy, int H, int W, int nc, float *coef, float *rhs);
+
+/*
  * Forward-backward consistency of two flows (Sundaram et al. 2010): where can
  * `fw` (frame 1 -> 2) be trusted, given `bw` (frame 2 -> 1)?  fw, bw planar
  * 2 x H x W.  For pixel (i, j), 0-based, u = fw.x, v = fw.y, in double from

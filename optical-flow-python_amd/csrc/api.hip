@@ -1,6 +1,19 @@
 // api.hip — the C entries (include/optflow.h) that are not batch calls:
 // context create and destroy, options, profiling, the solve log, the
 // single-pair calls, the stage entries of the parity tests and flow colour.
+namespace {
+// the caller's H x W data weight on the device, or p == nullptr without one;
+// its values and what it cannot be combined with are checked on the host
+// before anything is launched
+Img upload_weight(of_ctx *c, const of_params *P, const float *weight, int H, int W) {
+  if (!weight) return Img();
+  REQUIRE(P && H > 0 && W > 0, OF_EINVAL, "bad arguments");
+  check_weight_values(weight, H, W);
+  check_weight_params(P, true);
+  return upload_new_img(c, weight, H, W, 1);
+}
+}  // namespace
+
 extern "C" {
 
 int of_abi_version(void) { return OF_ABI_VERSION; }
@@ -284,16 +297,42 @@ int of_solver_geometry(int H, int W, int solver, of_cg_geometry *out) {
   return cg_geometry(H, W, solver == OF_SOLVER_BACKSLASH, out);
 }
 
-int of_estimate_flow(of_ctx *c, of_params *P, const float *im1, const float *im2, int H, int W, int C,
-                     const float *init_uv, float *out_uv, of_stats *st) {
+// The *_weighted entries carry their unweighted siblings' bodies: a NULL
+// weight uploads nothing and launches the unweighted kernels.
+int of_estimate_flow_weighted(of_ctx *c, of_params *P, const float *im1, const float *im2, int H, int W, int C,
+                              const float *init_uv, const float *weight, float *out_uv, of_stats *st) {
   API_BEGIN(c)
   REQUIRE(P && im1 && im2 && out_uv && H > 0 && W > 0, OF_EINVAL, "bad arguments");
+  const Img wgt = upload_weight(c, P, weight, H, W);
   if (st) memset(st, 0, sizeof(*st));
   const WallClock wall;
   float *d1, *d2;
   upload_frames(c, im1, im2, (size_t)H * W * C, &d1, &d2);
   F2 uv = init_flow(c, init_uv, H, W);
-  estimate_dev(c, P, d1, d2, false, H, W, C, uv, st);
+  estimate_dev(c, P, d1, d2, false, H, W, C, uv, st, wgt);
+  download_f2(c, uv, out_uv);
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (st) st->total_ms = wall.ms();
+  API_END(c)
+}
+
+int of_estimate_flow(of_ctx *c, of_params *P, const float *im1, const float *im2, int H, int W, int C,
+                     const float *init_uv, float *out_uv, of_stats *st) {
+  return of_estimate_flow_weighted(c, P, im1, im2, H, W, C, init_uv, nullptr, out_uv, st);
+}
+
+int of_compute_flow_weighted(of_ctx *c, of_params *P, const float *images, int H, int W, int nc, const float *guide,
+                             int gc, const float *init_uv, const float *weight, float *out_uv, of_stats *st) {
+  API_BEGIN(c)
+  REQUIRE(P && images && out_uv && H > 0 && W > 0 && nc >= 1, OF_EINVAL, "bad arguments");
+  const Img wgt = upload_weight(c, P, weight, H, W);
+  if (st) memset(st, 0, sizeof(*st));
+  const WallClock wall;
+  Img im = upload_new_img(c, images, H, W, 2 * nc);
+  Img g;
+  if (guide && gc > 0) g = upload_new_img(c, guide, H, W, gc);
+  F2 uv = init_flow(c, init_uv, H, W);
+  compute_flow_dev(c, P, im, g, uv, st, wgt);
   download_f2(c, uv, out_uv);
   HIPCHK(hipStreamSynchronize(c->stream));
   if (st) st->total_ms = wall.ms();
@@ -302,19 +341,7 @@ int of_estimate_flow(of_ctx *c, of_params *P, const float *im1, const float *im2
 
 int of_compute_flow(of_ctx *c, of_params *P, const float *images, int H, int W, int nc, const float *guide, int gc,
                     const float *init_uv, float *out_uv, of_stats *st) {
-  API_BEGIN(c)
-  REQUIRE(P && images && out_uv && H > 0 && W > 0 && nc >= 1, OF_EINVAL, "bad arguments");
-  if (st) memset(st, 0, sizeof(*st));
-  const WallClock wall;
-  Img im = upload_new_img(c, images, H, W, 2 * nc);
-  Img g;
-  if (guide && gc > 0) g = upload_new_img(c, guide, H, W, gc);
-  F2 uv = init_flow(c, init_uv, H, W);
-  compute_flow_dev(c, P, im, g, uv, st);
-  download_f2(c, uv, out_uv);
-  HIPCHK(hipStreamSynchronize(c->stream));
-  if (st) st->total_ms = wall.ms();
-  API_END(c)
+  return of_compute_flow_weighted(c, P, images, H, W, nc, guide, gc, init_uv, nullptr, out_uv, st);
 }
 
 int of_fb_consistency(of_ctx *c, const float *fw, const float *bw, int H, int W, double alpha1, double alpha2,
@@ -422,12 +449,14 @@ int of_estimate_interp(of_ctx *c, of_params *P, const float *im1, const float *i
   API_END(c)
 }
 
-int of_compute_flow_base(of_ctx *c, of_params *P, const float *images, int H, int W, int nc, const float *guide,
-                         int gc, double alpha, const float *uv_in, float *out_uv) {
+int of_compute_flow_base_weighted(of_ctx *c, of_params *P, const float *images, int H, int W, int nc,
+                                  const float *guide, int gc, double alpha, const float *uv_in, const float *weight,
+                                  float *out_uv) {
   API_BEGIN(c)
   REQUIRE(P && images && uv_in && out_uv, OF_EINVAL, "bad arguments");
   check_params(P);
   LevelIn L;
+  L.wgt = upload_weight(c, P, weight, H, W);
   L.im = upload_new_img(c, images, H, W, 2 * nc);
   if (guide && gc > 0 && P->method == OF_METHOD_CLASSIC_NL) L.guide = upload_new_img(c, guide, H, W, gc);
   F2 uv = upload_f2(c, uv_in, H, W);
@@ -439,6 +468,11 @@ int of_compute_flow_base(of_ctx *c, of_params *P, const float *images, int H, in
   download_f2(c, uv, out_uv);
   HIPCHK(hipStreamSynchronize(c->stream));
   API_END(c)
+}
+
+int of_compute_flow_base(of_ctx *c, of_params *P, const float *images, int H, int W, int nc, const float *guide,
+                         int gc, double alpha, const float *uv_in, float *out_uv) {
+  return of_compute_flow_base_weighted(c, P, images, H, W, nc, guide, gc, alpha, uv_in, nullptr, out_uv);
 }
 
 // AltBAOpticalFlow.compute_flow_base(uv, uvhat) (alt_ba.py:189-274): one
@@ -531,21 +565,28 @@ int of_partial_deriv(of_ctx *c, const float *images, int H, int W, int nc, const
   API_END(c)
 }
 
-int of_flow_operator(of_ctx *c, const of_params *P, double alpha, const float *uv, const float *duv, const float *It,
-                     const float *Ix, const float *Iy, int H, int W, int nc, float *coef, float *rhs) {
+int of_flow_operator_weighted(of_ctx *c, const of_params *P, double alpha, const float *uv, const float *duv,
+                              const float *weight, const float *It, const float *Ix, const float *Iy, int H, int W,
+                              int nc, float *coef, float *rhs) {
   API_BEGIN(c)
   REQUIRE(P && uv && It && Ix && Iy && coef && rhs && nc >= 1, OF_EINVAL, "bad arguments");
+  const Img wgt = upload_weight(c, P, weight, H, W);
   F2 f = upload_f2(c, uv, H, W);
   F2 df;
   if (duv) df = upload_f2(c, duv, H, W);
   Img a = upload_new_img(c, It, H, W, nc), b = upload_new_img(c, Ix, H, W, nc), d = upload_new_img(c, Iy, H, W, nc);
   Img cf = new_img(c, H, W, 7);
   F2 r = new_f2(c, H, W);
-  flow_operator(c, op_args(P, alpha, 0.0), f, duv ? &df : nullptr, a, b, d, nullptr, cf, r);
+  flow_operator(c, op_args(P, alpha, 0.0), f, duv ? &df : nullptr, a, b, d, nullptr, cf, r, wgt);
   download_img(c, cf, coef);
   download_f2(c, r, rhs);
   HIPCHK(hipStreamSynchronize(c->stream));
   API_END(c)
+}
+
+int of_flow_operator(of_ctx *c, const of_params *P, double alpha, const float *uv, const float *duv, const float *It,
+                     const float *Ix, const float *Iy, int H, int W, int nc, float *coef, float *rhs) {
+  return of_flow_operator_weighted(c, P, alpha, uv, duv, nullptr, It, Ix, Iy, H, W, nc, coef, rhs);
 }
 
 int of_solve(of_ctx *c, const of_params *P, const float *coef, const float *rhs, int H, int W, float *x, int *iters,

@@ -68,19 +68,35 @@ int pen_mode(const OpArgs &o) {
     default: f(KT<__VA_ARGS__ OF_PM_ANY>); break;                                          \
   }
 
+// a per-pixel data weight (include/optflow.h) must be a plane of the level,
+// pitched like the system's; the fp64 assembly (AltBA) has no weighted form
+void check_weight(const Img &wgt, const OpArgs &o, const Img &coef) {
+  REQUIRE(!o.f64, OF_ENOTSUP, "a data weight is not supported with AltBA (classic-c-a)");
+  REQUIRE(wgt.H == coef.H && wgt.W == coef.W && wgt.P == coef.P && wgt.C == 1, OF_EHIP,
+          "data weight: not a plane of this level");
+}
+
+// wgt: the level's data-weight plane, or p == nullptr (the unweighted kernels)
 void flow_operator(of_ctx *c, const OpArgs &o, const F2 &uv, const F2 *duv, const Img &It, const Img &Ix,
-                   const Img &Iy, const F2 *uvhat, const Img &coef, const F2 &rhs) {
+                   const Img &Iy, const F2 *uvhat, const Img &coef, const F2 &rhs, const Img &wgt = Img()) {
   Grid2 g = grid2(uv.H, uv.W);
-  auto f = [&](auto kern) {
+  auto go = [&](auto kern, auto... w) {
     launch(c, "flow_operator", kern, g.grid, g.block, 0, o, (const float2 *)uv.p,
            (const float2 *)(duv ? duv->p : nullptr), (const float *)It.p, (const float *)Ix.p, (const float *)Iy.p,
-           It.C, (const float2 *)(uvhat ? uvhat->p : nullptr), uv.H, uv.W, uv.P, coef.ps(), coef.p, rhs.p);
+           It.C, (const float2 *)(uvhat ? uvhat->p : nullptr), uv.H, uv.W, uv.P, coef.ps(), coef.p, rhs.p, w...);
   };
+  const int m = uvhat ? OF_PM_ANY : pen_mode(o);
+  if (wgt.p) {
+    check_weight(wgt, o, coef);
+    auto f = [&](auto kern) { go(kern, (const float *)wgt.p); };
+    OF_BY_PM(m, k_flow_operator_w, )
+    return;
+  }
+  auto f = [&](auto kern) { go(kern); };
   if (o.f64) {
     f(k_flow_operator_f64);
     return;
   }
-  const int m = uvhat ? OF_PM_ANY : pen_mode(o);
   OF_BY_PM(m, k_flow_operator, )
 }
 
@@ -89,8 +105,18 @@ void flow_operator(of_ctx *c, const OpArgs &o, const F2 &uv, const F2 *duv, cons
 bool can_fuse_warp_op(const of_ctx *c, const OpArgs &o, int nc) {
   return c->opt_fused_warp && !o.f64 && (nc == 1 || nc == 3);
 }
+// calls f(kernel) with the instantiation of KT for the interpolation, the
+// channel count (1 or 3) and the penalty mode
+#define OF_BY_INTERP_NC_PM(interp, one, m, KT)                                                \
+  if (interp == OF_INTERP_BICUBIC) {                                                          \
+    if (one) { OF_BY_PM(m, KT, 1, 1, ) } else { OF_BY_PM(m, KT, 1, 3, ) }                      \
+  } else if (interp == OF_INTERP_CUBIC) {                                                     \
+    if (one) { OF_BY_PM(m, KT, 0, 1, ) } else { OF_BY_PM(m, KT, 0, 3, ) }                      \
+  } else {                                                                                    \
+    if (one) { OF_BY_PM(m, KT, 2, 1, ) } else { OF_BY_PM(m, KT, 2, 3, ) }                      \
+  }
 void warp_operator(of_ctx *c, const LevelDeriv &L, int interp, const OpArgs &o, const F2 &uv, const Img &coef,
-                   const F2 &rhs) {
+                   const F2 &rhs, const Img &wgt = Img()) {
   Grid2 g = grid2(uv.H, uv.W);
   const size_t ps = coef.ps();
   REQUIRE(L.I1x.ps() == ps && L.args.nc == L.I1x.C, OF_EHIP, "warp_operator: plane strides differ");
@@ -98,15 +124,18 @@ void warp_operator(of_ctx *c, const LevelDeriv &L, int interp, const OpArgs &o, 
   const char *name = interp == OF_INTERP_BICUBIC ? "warp_operator_hermite"
                      : interp == OF_INTERP_CUBIC ? "warp_operator_bspline"
                                                  : "warp_operator_bilinear";
-  auto f = [&](auto kern) { launch(c, name, kern, g.grid, g.block, 0, L.args, o, u, uv.H, uv.W, uv.P, ps, coef.p, rhs.p); };
+  auto go = [&](auto kern, auto... w) {
+    launch(c, name, kern, g.grid, g.block, 0, L.args, o, u, uv.H, uv.W, uv.P, ps, coef.p, rhs.p, w...);
+  };
   const int m = pen_mode(o);
   const bool one = L.args.nc == 1;
-  if (interp == OF_INTERP_BICUBIC) {
-    if (one) { OF_BY_PM(m, k_warp_operator, 1, 1, ) } else { OF_BY_PM(m, k_warp_operator, 1, 3, ) }
-  } else if (interp == OF_INTERP_CUBIC) {
-    if (one) { OF_BY_PM(m, k_warp_operator, 0, 1, ) } else { OF_BY_PM(m, k_warp_operator, 0, 3, ) }
+  if (wgt.p) {
+    check_weight(wgt, o, coef);
+    auto f = [&](auto kern) { go(kern, (const float *)wgt.p); };
+    OF_BY_INTERP_NC_PM(interp, one, m, k_warp_operator_w)
   } else {
-    if (one) { OF_BY_PM(m, k_warp_operator, 2, 1, ) } else { OF_BY_PM(m, k_warp_operator, 2, 3, ) }
+    auto f = [&](auto kern) { go(kern); };
+    OF_BY_INTERP_NC_PM(interp, one, m, k_warp_operator)
   }
 }
 
@@ -114,6 +143,7 @@ void warp_operator(of_ctx *c, const LevelDeriv &L, int interp, const OpArgs &o, 
 struct LevelIn {
   Img im;     // 2*nc planes
   Img guide;  // gc planes or p == nullptr
+  Img wgt;    // the per-pixel data weight (one plane) or p == nullptr
 };
 
 // Lanes mode (of_pairs_run, of_pairs_run_host, the pair pool): every linear
@@ -204,10 +234,10 @@ void hs_base(of_ctx *c, const of_params *P, const LevelIn &L, F2 &uv, of_stats *
   const bool fuse = can_fuse_warp_op(c, o, nc);
   for (int it = 0; it < P->max_warping_iters; ++it) {
     if (fuse) {
-      warp_operator(c, D, P->interp, o, uv, coef, rhs);
+      warp_operator(c, D, P->interp, o, uv, coef, rhs, L.wgt);
     } else {
       partial_deriv(c, D, P->interp, uv, It, Ix, Iy);
-      flow_operator(c, o, uv, nullptr, It, Ix, Iy, nullptr, coef, rhs);
+      flow_operator(c, o, uv, nullptr, It, Ix, Iy, nullptr, coef, rhs, L.wgt);
     }
     note_solve(c, st, solve_tok(c, P, coef, rhs, x));
     c->cur_px = (double)H * W;
@@ -245,6 +275,7 @@ void irls_base(of_ctx *c, const of_params *P, const LevelIn &L, F2 &uv, double a
   Grid2 g = grid2(H, W);
   const bool nl = P->method == OF_METHOD_CLASSIC_NL;
   const bool gen = P->filters.general;
+  REQUIRE(!(gen && L.wgt.p), OF_ENOTSUP, "a data weight is not supported with a general spatial_filters list");
   GenLevel GL;
   if (gen) GL = gen_level(c, P, H, W);
   // one linearisation per warp: warp + assembly fused (no derivative planes)
@@ -256,10 +287,10 @@ void irls_base(of_ctx *c, const of_params *P, const LevelIn &L, F2 &uv, double a
         gen_flow_operator(c, P, o, uv, jl ? &duv : nullptr, It, Ix, Iy, nullptr, GL, rhs);
         note_solve(c, st, gen_solve_logged(c, P, GL, rhs, x));
       } else if (fuse) {
-        warp_operator(c, D, P->interp, o, uv, coef, rhs);
+        warp_operator(c, D, P->interp, o, uv, coef, rhs, L.wgt);
         note_solve(c, st, solve_tok(c, P, coef, rhs, x));
       } else {
-        flow_operator(c, o, uv, jl ? &duv : nullptr, It, Ix, Iy, nullptr, coef, rhs);
+        flow_operator(c, o, uv, jl ? &duv : nullptr, It, Ix, Iy, nullptr, coef, rhs, L.wgt);
         note_solve(c, st, solve_tok(c, P, coef, rhs, x));
       }
       c->cur_px = (double)H * W;
@@ -372,11 +403,26 @@ void check_params(const of_params *P) {
   }
 }
 
+// what a data weight cannot be combined with, refused before any launch
+void check_weight_params(const of_params *P, bool weighted) {
+  if (!weighted) return;
+  REQUIRE(!P->filters.general, OF_ENOTSUP, "a data weight is not supported with a general spatial_filters list");
+  REQUIRE(P->method != OF_METHOD_ALT_BA, OF_ENOTSUP, "a data weight is not supported with AltBA (classic-c-a)");
+}
+
+// a host weight plane (H x W dense): finite and >= 0, checked before any launch
+void check_weight_values(const float *w, int H, int W) {
+  const size_t n = (size_t)H * W;
+  for (size_t k = 0; k < n; ++k)
+    REQUIRE(std::isfinite(w[k]) && w[k] >= 0.0f, OF_EINVAL, "the data weight must be finite and >= 0");
+}
+
 // The pyramids one compute_flow runs on: the texture (or scaled) pair's for
 // the first GNC stage and for the later ones, and the weighted median's colour
 // guide's when Classic+NL has one
 struct FlowPyr {
   std::vector<Img> pyr, gpyr, cpyr, cgpyr;
+  std::vector<Img> wpyr, wgpyr;  // the data weight's own pyramids (empty: no weight)
   int levels = 0;
   bool use_guide = false;
 };
@@ -392,7 +438,8 @@ void guide_pyramids(of_ctx *c, const of_params *P, const Img &guide, FlowPyr &F)
 // compute_flow, first half: preprocessing and pyramids (hs.py:49-75,
 // ba.py:57-99, classic_nl.py:89-139, alt_ba.py:81-126)
 // images: device 2nc planes; guide: device gc planes or p == nullptr
-FlowPyr flow_pyramids(of_ctx *c, of_params *P, const Img &images, const Img &guide) {
+// weight: the full-resolution data weight (one plane) or p == nullptr
+FlowPyr flow_pyramids(of_ctx *c, of_params *P, const Img &images, const Img &guide, const Img &weight = Img()) {
   const int H = images.H, W = images.W, C = images.C, nc = C / 2;
   REQUIRE(nc >= 1 && nc <= OF_MAX_NC, OF_ENOTSUP, "1..4 channels per frame supported");
   Img img;
@@ -425,6 +472,12 @@ FlowPyr flow_pyramids(of_ctx *c, of_params *P, const Img &images, const Img &gui
   F.pyr = build_pyramid(c, img, levels, P->pyramid_spacing);
   if (P->method != OF_METHOD_HS) F.gpyr = build_pyramid(c, img, P->gnc_pyramid_levels, P->gnc_pyramid_spacing);
   guide_pyramids(c, P, guide, F);
+  if (weight.p) {
+    // the Gaussian and the bilinear resize the frames get: convex
+    // combinations, so every level stays >= 0
+    F.wpyr = build_pyramid(c, weight, levels, P->pyramid_spacing);
+    if (P->method != OF_METHOD_HS) F.wgpyr = build_pyramid(c, weight, P->gnc_pyramid_levels, P->gnc_pyramid_spacing);
+  }
   return F;
 }
 
@@ -475,6 +528,7 @@ void run_schedule(of_ctx *c, of_params *P, const FlowPyr &F, F2 &uv_io, of_stats
       LevelIn L;
       L.im = lv[l];
       if (use_guide) L.guide = (ig == 0 ? cpyr : cgpyr)[l];
+      if (!F.wpyr.empty()) L.wgt = (ig == 0 ? F.wpyr : F.wgpyr)[l];
       if (P->method == OF_METHOD_HS) hs_base(c, P, L, uv, st);
       else if (P->method == OF_METHOD_ALT_BA) altba_base(c, P, L, uv, uvhat, P->alpha, ig != gnc - 1, st);
       else irls_base(c, P, L, uv, P->alpha, ig == 0 ? 1 : P->max_linear, st);
@@ -537,12 +591,15 @@ void add_preprocess_ms(of_stats *st, hipEvent_t t0, hipEvent_t t1) {
 // compute_flow (hs.py:49-99, ba.py:57-138, classic_nl.py:89-198, alt_ba.py:81-187)
 // images: device 2nc planes; guide: device gc planes or p == nullptr;
 // uv_io: full-resolution flow (init in, result out).
-void compute_flow_dev(of_ctx *c, of_params *P, const Img &images, const Img &guide, F2 &uv_io, of_stats *st) {
+// weight: the per-pixel data weight (one plane) or p == nullptr
+void compute_flow_dev(of_ctx *c, of_params *P, const Img &images, const Img &guide, F2 &uv_io, of_stats *st,
+                      const Img &weight = Img()) {
   check_params(P);
+  check_weight_params(P, weight.p != nullptr);
   hipEvent_t t0 = timing_event(c), t1 = timing_event(c);
   HIPCHK(hipEventRecord(t0, c->stream));
   c->prog_t0 = std::chrono::steady_clock::now();
-  const FlowPyr F = flow_pyramids(c, P, images, guide);
+  const FlowPyr F = flow_pyramids(c, P, images, guide, weight);
   HIPCHK(hipEventRecord(t1, c->stream));
   run_schedule(c, P, F, uv_io, st);
   add_preprocess_ms(st, t0, t1);
@@ -551,8 +608,9 @@ void compute_flow_dev(of_ctx *c, of_params *P, const Img &images, const Img &gui
 // estimate_flow preprocessing (interface.py:41-64): host or device RGB input
 // rgb1/rgb2: (H, W, C) frames on the device, fp32 or (u8) bytes
 void estimate_dev(of_ctx *c, of_params *P, const void *rgb1, const void *rgb2, bool u8, int H, int W, int C, F2 &uv,
-                  of_stats *st) {
+                  of_stats *st, const Img &weight = Img()) {
   REQUIRE(C == 1 || C == 3, OF_EINVAL, "images must be (H,W) or (H,W,3)");
+  check_weight_params(P, weight.p != nullptr);
   hipEvent_t t0 = timing_event(c), t1 = timing_event(c);
   HIPCHK(hipEventRecord(t0, c->stream));
   Img gray = new_img(c, H, W, 2);
@@ -562,7 +620,7 @@ void estimate_dev(of_ctx *c, of_params *P, const void *rgb1, const void *rgb2, b
   if (u8) rgb_prep(c, (const uint8_t *)rgb1, (const uint8_t *)rgb2, H, W, C, gray, guide);
   else rgb_prep(c, (const float *)rgb1, (const float *)rgb2, H, W, C, gray, guide);
   HIPCHK(hipEventRecord(t1, c->stream));
-  compute_flow_dev(c, P, gray, guide, uv, st);
+  compute_flow_dev(c, P, gray, guide, uv, st, weight);
   add_preprocess_ms(st, t0, t1);
 }
 

@@ -228,12 +228,15 @@ __device__ __forceinline__ UvNbr ld_nbr(const float2 *__restrict__ uv, int i, in
 // One pixel's row of the system; deriv(ch, It, Ix, Iy) fetches channel ch's
 // derivatives (planes, or the fused kernel's registers).  nb: the flow of
 // the pixel and its neighbours already in registers (ld_nbr; only without
-// duv), else loaded here.
-template <int NC, int M, typename Deriv>
+// duv), else loaded here.  WT: the data term carries the per-pixel weight
+// wgt[k] (a plane pitched like an Img plane; include/optflow.h, "Per-pixel
+// data-term weights"): psi * wgt[k], one fp32 product, stands in for psi.
+template <int NC, int M, bool WT, typename Deriv>
 __device__ __forceinline__ void assemble_px(const OpArgs &o, const float2 *__restrict__ uv,
                                             const float2 *__restrict__ duv, int nc_rt, const float2 *__restrict__ uvhat,
                                             int i, int j, int H, int W, int P, size_t ps, float *__restrict__ coef,
-                                            float2 *__restrict__ rhs, const Deriv &deriv, const UvNbr *nb = nullptr) {
+                                            float2 *__restrict__ rhs, const float *__restrict__ wgt, const Deriv &deriv,
+                                            const UvNbr *nb = nullptr) {
   OF_NOCONTRACT
   using PM = PenMode<M>;
   const int nc = NC > 0 ? NC : nc_rt;
@@ -259,7 +262,8 @@ __device__ __forceinline__ void assemble_px(const OpArgs &o, const float2 *__res
     itx += itl * gx; ity += itl * gy;
   }
   const float inv = 1.0f / (float)nc;
-  const float psi = ((PM::q(o) ? o.aq_d * psq : 0.f) + (PM::r(o) ? o.ar_d * psr : 0.f)) * inv;
+  float psi = ((PM::q(o) ? o.aq_d * psq : 0.f) + (PM::r(o) ? o.ar_d * psr : 0.f)) * inv;
+  if (WT) psi = psi * wgt[k];
   ix2 *= inv; iy2 *= inv; ixy *= inv; itx *= inv; ity *= inv;
   // b uses uv (not uv + duv): classic_nl.py:362-367
   const float2 u0 = nb ? nb->c : uv[k];
@@ -289,6 +293,10 @@ __device__ __forceinline__ void assemble_px(const OpArgs &o, const float2 *__res
   rhs[k] = make_float2(bu, bv);
 }
 
+// The unweighted assembly kernels keep their names, signatures and bodies, so
+// their code stays instruction for instruction what it was (tools/isa_diff.py);
+// the weighted forms are kernels of their own (k_*_w) that take the weight
+// plane as their last argument and differ in nothing else.
 template <int M>
 __global__ __launch_bounds__(OF_BX *OF_BY) void k_flow_operator(OpArgs o, const float2 *__restrict__ uv, const float2 *__restrict__ duv,
                                 const float *__restrict__ It, const float *__restrict__ Ix, const float *__restrict__ Iy,
@@ -297,7 +305,25 @@ __global__ __launch_bounds__(OF_BX *OF_BY) void k_flow_operator(OpArgs o, const 
   OF_FOR_PIXELS_XCD(H, W) {
     if (j >= W) continue;
     const size_t k = (size_t)i * P + j;
-    assemble_px<0, M>(o, uv, duv, nc, uvhat, i, j, H, W, P, ps, coef, rhs, [&](int ch, float &it, float &gx, float &gy) {
+    assemble_px<0, M, false>(o, uv, duv, nc, uvhat, i, j, H, W, P, ps, coef, rhs, nullptr,
+                             [&](int ch, float &it, float &gx, float &gy) {
+      const size_t kc = ch * ps + k;
+      it = It[kc];
+      gx = Ix[kc];
+      gy = Iy[kc];
+    });
+  }
+}
+template <int M>
+__global__ __launch_bounds__(OF_BX *OF_BY) void k_flow_operator_w(OpArgs o, const float2 *__restrict__ uv, const float2 *__restrict__ duv,
+                                const float *__restrict__ It, const float *__restrict__ Ix, const float *__restrict__ Iy,
+                                int nc, const float2 *__restrict__ uvhat, int H, int W, int P, size_t ps,
+                                float *__restrict__ coef, float2 *__restrict__ rhs, const float *__restrict__ wgt) {
+  OF_FOR_PIXELS_XCD(H, W) {
+    if (j >= W) continue;
+    const size_t k = (size_t)i * P + j;
+    assemble_px<0, M, true>(o, uv, duv, nc, uvhat, i, j, H, W, P, ps, coef, rhs, wgt,
+                            [&](int ch, float &it, float &gx, float &gy) {
       const size_t kc = ch * ps + k;
       it = It[kc];
       gx = Ix[kc];
@@ -324,19 +350,46 @@ __global__ __launch_bounds__(OF_BX *OF_BY) void k_warp_operator(DerivArgs d, OpA
     const float2 f = nb.c;
     RegOut<NC> r;
     warp_pixel<INTERP, NC>(d, H, W, P, ps, i, j, (float)(j + 1) + f.x, (float)(i + 1) + f.y, r);
-    assemble_px<NC, M>(o, uv, (const float2 *)nullptr, NC, (const float2 *)nullptr, i, j, H, W, P, ps, coef, rhs,
-                    [&](int ch, float &it, float &gx, float &gy) {
-                      it = r.it[ch];
-                      gx = r.ix[ch];
-                      gy = r.iy[ch];
-                    }, &nb);
+    assemble_px<NC, M, false>(o, uv, (const float2 *)nullptr, NC, (const float2 *)nullptr, i, j, H, W, P, ps, coef, rhs,
+                              nullptr, [&](int ch, float &it, float &gx, float &gy) {
+                                it = r.it[ch];
+                                gx = r.ix[ch];
+                                gy = r.iy[ch];
+                              }, &nb);
   }
 }
-#define OF_WOP(I, N, M) template __global__ void k_warp_operator<I, N, M>(DerivArgs, OpArgs, const float2 *, int, int, \
-                                                                          int, size_t, float *, float2 *);
-#define OF_FOP(M) template __global__ void k_flow_operator<M>(OpArgs, const float2 *, const float2 *, const float *, \
-                                                              const float *, const float *, int, const float2 *, int, \
-                                                              int, int, size_t, float *, float2 *);
+// the same with the data weight (k_partial_deriv + k_flow_operator_w, bitwise)
+template <int INTERP, int NC, int M>
+__global__ __launch_bounds__(OF_BX *OF_BY) void k_warp_operator_w(DerivArgs d, OpArgs o, const float2 *__restrict__ uv,
+                                                                  int H, int W, int P, size_t ps,
+                                                                  float *__restrict__ coef, float2 *__restrict__ rhs,
+                                                                  const float *__restrict__ wgt) {
+  OF_FOR_PIXELS_XCD(H, W) {
+    if (j >= W) continue;
+    const UvNbr nb = ld_nbr(uv, i, j, H, W, P);
+    const float2 f = nb.c;
+    RegOut<NC> r;
+    warp_pixel<INTERP, NC>(d, H, W, P, ps, i, j, (float)(j + 1) + f.x, (float)(i + 1) + f.y, r);
+    assemble_px<NC, M, true>(o, uv, (const float2 *)nullptr, NC, (const float2 *)nullptr, i, j, H, W, P, ps, coef, rhs,
+                             wgt, [&](int ch, float &it, float &gx, float &gy) {
+                               it = r.it[ch];
+                               gx = r.ix[ch];
+                               gy = r.iy[ch];
+                             }, &nb);
+  }
+}
+#define OF_WOP(I, N, M)                                                                                             \
+  template __global__ void k_warp_operator<I, N, M>(DerivArgs, OpArgs, const float2 *, int, int, int, size_t, float *, \
+                                                    float2 *);                                                     \
+  template __global__ void k_warp_operator_w<I, N, M>(DerivArgs, OpArgs, const float2 *, int, int, int, size_t,      \
+                                                      float *, float2 *, const float *);
+#define OF_FOP(M)                                                                                                   \
+  template __global__ void k_flow_operator<M>(OpArgs, const float2 *, const float2 *, const float *, const float *,  \
+                                              const float *, int, const float2 *, int, int, int, size_t, float *,    \
+                                              float2 *);                                                           \
+  template __global__ void k_flow_operator_w<M>(OpArgs, const float2 *, const float2 *, const float *, const float *, \
+                                                const float *, int, const float2 *, int, int, int, size_t, float *,  \
+                                                float2 *, const float *);
 // specialised penalty modes: the registry's quadratic stage and its robust
 // stages (generalized Charbonnier: Classic+NL; Charbonnier: Classic-C;
 // Lorentzian: BA; Horn-Schunck's constant weights)

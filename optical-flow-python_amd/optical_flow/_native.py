@@ -43,6 +43,14 @@ _SIGS = {
                           C.POINTER(OfStats)], C.c_int),
     "of_compute_flow": ([_vp, C.POINTER(OfParams), _fp, C.c_int, C.c_int, C.c_int, _fp, C.c_int, _fp, _fp,
                          C.POINTER(OfStats)], C.c_int),
+    "of_estimate_flow_weighted": ([_vp, C.POINTER(OfParams), _fp, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp,
+                                   C.POINTER(OfStats)], C.c_int),
+    "of_compute_flow_weighted": ([_vp, C.POINTER(OfParams), _fp, C.c_int, C.c_int, C.c_int, _fp, C.c_int, _fp, _fp,
+                                  _fp, C.POINTER(OfStats)], C.c_int),
+    "of_compute_flow_base_weighted": ([_vp, C.POINTER(OfParams), _fp, C.c_int, C.c_int, C.c_int, _fp, C.c_int,
+                                       C.c_double, _fp, _fp, _fp], C.c_int),
+    "of_flow_operator_weighted": ([_vp, C.POINTER(OfParams), C.c_double, _fp, _fp, _fp, _fp, _fp, _fp, C.c_int,
+                                   C.c_int, C.c_int, _fp, _fp], C.c_int),
     "of_fb_consistency": ([_vp, _fp, _fp, C.c_int, C.c_int, C.c_double, C.c_double, _u8p, _fp], C.c_int),
     "of_estimate_flow_bidir": ([_vp, C.POINTER(OfParams), _fp, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp,
                                 C.c_double, C.c_double, _u8p, _u8p, C.POINTER(OfStats), C.POINTER(OfStats)],
@@ -238,6 +246,24 @@ def u8ptr(a):
 
 def dptr(a):
     return None if a is None else a.ctypes.data_as(_dp)
+
+
+def data_weight(w, H, W):
+    """The per-pixel data-term weight as the C ABI takes it (include/optflow.h,
+    "Per-pixel data-term weights"): contiguous (H, W) float32, or None.
+    ValueError for a wrong shape or a value that is not finite and >= 0."""
+    if w is None:
+        return None
+    w = np.asarray(w)
+    if w.shape != (H, W):
+        raise ValueError(f"data_weight must be ({H}, {W}), got {w.shape}")
+    if w.dtype == bool:
+        w = w.astype(np.float32)
+    with np.errstate(over='ignore'):
+        w = f32(w)
+    if not np.all(np.isfinite(w) & (w >= 0)):
+        raise ValueError("data_weight must be finite and >= 0 everywhere")
+    return w
 
 
 def planar(a):

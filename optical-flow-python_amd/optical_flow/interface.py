@@ -14,23 +14,38 @@ from optical_flow.methods.base import progress_printer
 from optical_flow.methods.config import load_of_method
 
 
-def estimate_flow(im1, im2, method='classic+nl-fast', params=None, gt=None):
+def estimate_flow(im1, im2, method='classic+nl-fast', params=None, gt=None, data_weight=None):
     """Flow (H, W, 2) float64 from im1 to im2; (H, W) or (H, W, >=3) inputs.
     Prints what the reference's compute_flow prints.  `gt` (an extension:
     the reference's estimate_flow has no such argument) is handed to the
-    per-GNC-stage report as compute_flow(init, gt) would get it."""
+    per-GNC-stage report as compute_flow(init, gt) would get it.
+
+    `data_weight` (an extension too): an (H, W) plane, finite and >= 0 (not
+    limited to <= 1; a bool mask works), that multiplies the data term of
+    every pixel of im1 (include/optflow.h, "Per-pixel data-term weights").
+    Where it is 0 -- a dead sensor region, a letterbox bar, a burnt-in
+    overlay, a masked boundary, pixels a forward-backward check flagged -- the
+    pixel's brightness constancy is switched off and the smoothness term
+    inpaints the flow from the surroundings; the coarse pyramid levels use
+    the weight's own pyramid.  The masked pixels' content still enters the
+    global min / max of the preprocessing and the blurred coarse frames, so
+    fill them with plausible values rather than extremes.  None is the
+    unweighted flow, bitwise.  A wrong shape or a NaN, Inf or negative value
+    raises ValueError; a general spatial_filters list or 'classic-c-a' with a
+    weight raises NotImplementedError."""
     im1 = np.asarray(im1, dtype=float)
     im2 = np.asarray(im2, dtype=float)
     ope = load_of_method(method)
     if params is not None:
         ope.parse_input_parameter(params)
     H, W = im1.shape[:2]
+    wgt = nat.data_weight(data_weight, H, W)
     if im1.ndim == 3 and im1.shape[2] < 3:
         # interface.py:47: channels are concatenated, no colour conversion
         ope.images = np.concatenate([im1, im2], axis=2)
         if ope.color_images is not None:
             ope.color_images = im1.copy()
-        return ope.compute_flow(np.zeros((H, W, 2)), gt)
+        return ope.compute_flow(np.zeros((H, W, 2)), gt, data_weight=wgt)
     if im1.ndim == 3:
         a = nat.f32(im1[:, :, :3])
         b = nat.f32(im2[:, :, :3])
@@ -44,8 +59,8 @@ def estimate_flow(im1, im2, method='classic+nl-fast', params=None, gt=None):
     ctx = nat.context()
     fn, flags = progress_printer(ope, gt)  # the reference's compute_flow prints (interface.py:66)
     with ctx.progress(fn, flags):
-        ctx.check(ctx.lib.of_estimate_flow(ctx.handle, C.byref(P), nat.ptr(a), nat.ptr(b), H, W, Cc, None,
-                                           nat.ptr(out), C.byref(st)))
+        ctx.check(ctx.lib.of_estimate_flow_weighted(ctx.handle, C.byref(P), nat.ptr(a), nat.ptr(b), H, W, Cc, None,
+                                                    nat.ptr(wgt), nat.ptr(out), C.byref(st)))
     ope.alpha = P.alpha
     ope.last_stats = st.as_dict()
     return nat.interleaved(out)

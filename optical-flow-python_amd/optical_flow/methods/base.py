@@ -282,13 +282,16 @@ class BaseOpticalFlow(ABC):
         g = nat.planar(g)
         return g, g.shape[0]
 
-    def compute_flow(self, init=None, gt=None):
+    def compute_flow(self, init=None, gt=None, *, data_weight=None):
         """GNC x coarse-to-fine x IRLS on the GPU (hs.py:49-99, ba.py:57-138,
         classic_nl.py:89-198, alt_ba.py:81-187).  Prints what the reference
         prints (display lines, the per-GNC-stage report with AAE/STD/EPE
-        against `gt`) from the library's progress events (of_set_progress)."""
+        against `gt`) from the library's progress events (of_set_progress).
+        `data_weight` (an extension, as in estimate_flow): an (H, W) plane,
+        finite and >= 0, that scales the data term per pixel."""
         images, H, W, nc = self._images_planar()
         guide, gc = self._guide_planar(H, W)
+        wgt = nat.data_weight(data_weight, H, W)
         P = self.to_params()
         init_p = None if init is None else nat.planar(init)
         out = np.empty((2, H, W), dtype=np.float32)
@@ -296,41 +299,46 @@ class BaseOpticalFlow(ABC):
         ctx = nat.context()
         fn, flags = progress_printer(self, gt)
         with ctx.progress(fn, flags):
-            ctx.check(ctx.lib.of_compute_flow(ctx.handle, C.byref(P), nat.ptr(images), H, W, nc,
-                                              nat.ptr(guide), gc, nat.ptr(init_p), nat.ptr(out), C.byref(st)))
+            ctx.check(ctx.lib.of_compute_flow_weighted(ctx.handle, C.byref(P), nat.ptr(images), H, W, nc,
+                                                       nat.ptr(guide), gc, nat.ptr(init_p), nat.ptr(wgt),
+                                                       nat.ptr(out), C.byref(st)))
         self.alpha = P.alpha
         if self._METHOD in ('hs', 'alt_ba') or getattr(self, 'auto_level', False):
             self.pyramid_levels = P.pyramid_levels
         self.last_stats = st.as_dict()
         return nat.interleaved(out)
 
-    def compute_flow_base(self, uv):
+    def compute_flow_base(self, uv, *, data_weight=None):
         """One pyramid level (hs.py:109-142, ba.py:143-206, classic_nl.py:200-277)
-        with the current images / color_images / alpha."""
+        with the current images / color_images / alpha; `data_weight` is used
+        as given, for this level."""
         images, H, W, nc = self._images_planar()
         guide, gc = self._guide_planar(H, W)
+        wgt = nat.data_weight(data_weight, H, W)
         P = self.to_params()
         uvp = nat.planar(uv)
         out = np.empty((2, H, W), dtype=np.float32)
         ctx = nat.context()
         fn, flags = progress_printer(self, None)
         with ctx.progress(fn, flags):
-            ctx.check(ctx.lib.of_compute_flow_base(ctx.handle, C.byref(P), nat.ptr(images), H, W, nc,
-                                                   nat.ptr(guide), gc, float(self.alpha), nat.ptr(uvp), nat.ptr(out)))
+            ctx.check(ctx.lib.of_compute_flow_base_weighted(ctx.handle, C.byref(P), nat.ptr(images), H, W, nc,
+                                                            nat.ptr(guide), gc, float(self.alpha), nat.ptr(uvp),
+                                                            nat.ptr(wgt), nat.ptr(out)))
         return nat.interleaved(out)
 
-    def _operator_planes(self, uv, duv, It, Ix, Iy, alpha):
+    def _operator_planes(self, uv, duv, It, Ix, Iy, alpha, data_weight=None):
         uv = np.asarray(uv, dtype=float)
         H, W = uv.shape[:2]
+        wgt = nat.data_weight(data_weight, H, W)
         It = np.asarray(It, dtype=float)
         nc = 1 if It.ndim == 2 else It.shape[2]
         P = self.to_params()
         coef = np.empty((7, H, W), dtype=np.float32)
         rhs = np.empty((2, H, W), dtype=np.float32)
         ctx = nat.context()
-        ctx.check(ctx.lib.of_flow_operator(
+        ctx.check(ctx.lib.of_flow_operator_weighted(
             ctx.handle, C.byref(P), float(alpha), nat.ptr(nat.planar(uv)),
-            nat.ptr(None if duv is None else nat.planar(duv)), nat.ptr(nat.planar(It)),
+            nat.ptr(None if duv is None else nat.planar(duv)), nat.ptr(wgt), nat.ptr(nat.planar(It)),
             nat.ptr(nat.planar(Ix)), nat.ptr(nat.planar(Iy)), H, W, nc, nat.ptr(coef), nat.ptr(rhs)))
         return coef, rhs
 
