@@ -532,7 +532,9 @@ typedef struct of_cg_geometry {
   int32_t rows;            /* rows per band */
   int32_t bands;
   int32_t blocks;          /* grid_x * grid_y */
-  int32_t strip_cols;      /* output columns per strip */
+  int32_t strip_cols;      /* output columns of the widest strip (k_cgs: an
+                            * edge strip, 120; 128 when one strip covers
+                            * the level; interior strips 112) */
 } of_cg_geometry;
 int of_solver_geometry(int H, int W, int solver, of_cg_geometry *out);
 

@@ -149,7 +149,7 @@ struct LevelIn {
 // Lanes mode (of_pairs_run, of_pairs_run_host, the pair pool): every linear
 // solve on a level of >= big_px pixels (solve_tok below) holds one of the
 // lanes' token slots (OF_TOKEN_SLOTS = 2) until its GPU work has drained, and
-// runs its k_cgs launches with CGS_LANES_BLOCKS (252, one per CU) blocks, so
+// runs its k_cgs launches with CGS_LANES_BLOCKS (256, one per CU) blocks, so
 // two fine solves of different pairs fill the chip side by side with bands
 // twice as tall as one solve's 504 blocks would have.  Until round 3 the token
 // had one slot and a fine solve 504 blocks (two lanes' 504-block launches

@@ -206,14 +206,20 @@ void cheb_poly(int m, double a, double b, double *cB) {
 #endif
 // k_cgs blocks of a fine solve in lanes mode, where OF_TOKEN_SLOTS (2) fine
 // solves of different pairs run side by side: one block per CU each, so a
-// band is twice as tall (R = 78 at 1080p) and walks R + 19 row steps for R
-// rows instead of 39 + 19 (the band halo is recomputed once per band).
+// band is twice as tall (R = 72 at 1080p; 78 at 18 strips) and walks R + 20
+// row steps for R rows instead of 36 + 20 (the band halo is recomputed once
+// per band).
 // Measured (round 3, 2 x 2 reps): 1 slot x 504 blocks 38.9, 2 x 504 40.7,
 // 2 x 336 42.8, 2 x 252 44.4 (4 lanes: 45.3), 2 x 200 42.9, 3 x 168 45.0,
 // 4 x 128 42.6 pairs/s (profiles/r3y_token_slots_ab.log, r3z_ab.log); 2 x 270
-// (15 bands) 42.2, 3 x 252 44.3 vs 44.8 (profiles/r3ak_ab.log)
+// (15 bands) 42.2, 3 x 252 44.3 vs 44.8 (profiles/r3ak_ab.log).  All of
+// those at 18 strips per 1080p row (14 bands of 78 rows at 252).  With the
+// edge strips owning their outer halo lanes 1920 columns are 17 strips, and
+// a target of 256 gives 15 bands of 72 rows (15 x 72 = 1080, 255 blocks,
+// still one per CU): 92 row steps per launch instead of 98.  864 x 1536
+// keeps its 14 strips x 18 bands.  (profiles/cgs_edge_strips/)
 #ifndef CGS_LANES_BLOCKS
-#define CGS_LANES_BLOCKS 252
+#define CGS_LANES_BLOCKS 256
 #endif
 // ... of a fine solve below 1.5 Mpx (864 x 1536, stage 2's first level):
 // 168 / 196 / 336 measured 43.6 / 44.0 / 43.6 vs 44.9 pairs/s at 252
@@ -239,7 +245,9 @@ void cheb_poly(int m, double a, double b, double *cB) {
 int cg_geometry(int H, int W, bool split, of_cg_geometry *g, int target_blocks = CGS_TARGET_BLOCKS) {
   if (H < 1 || W < 1) return OF_EINVAL;
   const int sw = split ? PCG_SWP : PCG_SW;
-  const int nstrips = (W + sw - 1) / sw;
+  // k_cgs: the first and the last strip also own their outer halo lanes
+  // (2 CGS_HALO columns each), so n strips cover PCG_SWP n + 4 CGS_HALO columns
+  const int nstrips = split ? std::max(1, (W - 4 * CGS_HALO + sw - 1) / sw) : (W + sw - 1) / sw;
   if (nstrips > PCG_MAX_BLOCKS) return OF_ENOTSUP;
   int nbands, R, gy;
   if (split) {
@@ -263,7 +271,8 @@ int cg_geometry(int H, int W, bool split, of_cg_geometry *g, int target_blocks =
   g->rows = R;
   g->bands = nbands;
   g->blocks = nstrips * gy;
-  g->strip_cols = sw;
+  // k_cgs: the widest strip is an edge strip (both edges when it is alone)
+  g->strip_cols = !split ? sw : sw + (nstrips == 1 ? 4 : 2) * CGS_HALO;
   return g->blocks <= PCG_MAX_BLOCKS ? OF_OK : OF_ENOTSUP;
 }
 

@@ -533,7 +533,20 @@ __global__ __launch_bounds__(256) void k_cg(PcgArgs g, int k, int R, int nbands)
 // T3 = v1.N v1, T4 = v2.N v1, T5 = v2.N v2 (each edge counted once, by its
 // right / lower pixel).
 // Seven stencil stages deep, so a strip carries four halo lanes per side
-// (PCG_SWP = 112 output columns, lanes 4..59).  Arithmetic is on (u, v)
+// towards a neighbouring strip: strip t holds columns [112 t, 112 t + 128)
+// (lane l: columns 112 t + 2 l and + 1) and owns lanes 4..59 (PCG_SWP = 112
+// output columns).  The halo only recomputes the neighbour's pixels, so the
+// side of a strip that has no neighbour needs none: the first strip also
+// owns lanes 0..3 and the last strip lanes 60..63, i.e. 120 + 112 (n - 2) +
+// 120 columns over n strips (17 at 1920, not 18) and all 128 when one strip
+// covers the level.  Those lanes are exact as they stand: cg_from_left /
+// cg_from_right are wave_shr:1 / wave_shl:1 DPP moves with bound_ctrl, so
+// lane 0 reads 0 as its left value and left weight (cgr_nsum's L and wl, T5's
+// h0) and lane 63 reads 0 as its right value (Rt), which is the operator at
+// the image's first and last column; columns >= W load 0 through CG_OOB, are
+// stored nowhere and count in no dot product (ok0 / ok1 in soff8, dm0, dm1
+// and the mask on p), and the ODD instances zero the pixel at column W.
+// Arithmetic is on (u, v)
 // pairs of one pixel (packed fp32: v_pk_fma_f32).  Each row's coefficients
 // are staged once into an LDS ring of records (per pixel the (u, v) weight
 // pairs of the edges right and below and D^-1 as (ia, ic), (ic, id)) that
@@ -1223,9 +1236,13 @@ __global__ __launch_bounds__(256) void k_cgs(PcgArgs g, int k, int R, int nbands
   // co-resident blocks differently on the SIMDs, role = wid ^ f(block), was
   // no faster: 51.5-54 vs 52 us per 1080p launch)
   const int role = wid;
-  const int jc = (tile - band * gridDim.x) * PCG_SWP - 2 * CGS_HALO + 2 * lane;
-  const bool ok0 = jc >= 0 && jc < W, ok1 = jc + 1 < W && jc >= 0;
-  const bool out_lane = lane >= CGS_HALO && lane < 64 - CGS_HALO;
+  // strip tx spans columns [PCG_SWP tx, PCG_SWP tx + 128): lanes 4..59 are
+  // output; the first strip's lanes 0..3 and the last strip's lanes 60..63
+  // have no neighbouring strip to recompute for, so they are output too
+  const int tx = tile - band * gridDim.x;
+  const int jc = tx * PCG_SWP + 2 * lane;
+  const bool ok0 = jc < W, ok1 = jc + 1 < W;
+  const bool out_lane = (lane >= CGS_HALO || tx == 0) && (lane < 64 - CGS_HALO || tx == (int)gridDim.x - 1);
   const unsigned off4 = ok0 ? (unsigned)jc * 4u : CG_OOB, off8 = ok0 ? (unsigned)jc * 8u : CG_OOB;
   const unsigned soff8 = ok0 && out_lane ? (unsigned)jc * 8u : CG_OOB;
   const bool live = band < nbands;

@@ -60,7 +60,7 @@ int main(int argc, char **argv) {
   hp[4 * PCG_MAX_BLOCKS] = 1.0;  // rr
   CK(hipMemcpy(part, hp.data(), hp.size() * 8, hipMemcpyHostToDevice));
   // same geometry as the library (host_solve.hip cg_geometry, split = k_cgs)
-  const int nstrips = (W + PCG_SWP - 1) / PCG_SWP;
+  const int nstrips = std::max(1, (W - 4 * CGS_HALO + PCG_SWP - 1) / PCG_SWP);
   int nbands = std::max(1, std::min((H + 7) / 8, PCG_MAX_BLOCKS / nstrips));
   const int R = (H + nbands - 1) / nbands;
   nbands = (H + R - 1) / R;

@@ -1,7 +1,7 @@
 """Aggregate HBM roofline of the fine CG solves as the timed lanes run them
-(two solves side by side, each with CGS_LANES_BLOCKS = 252 k_cgs blocks),
+(two solves side by side, each with at most CGS_LANES_BLOCKS = 256 k_cgs blocks),
 from a rocprofv3 kernel trace of the default bench (tools/profile.sh, pass 1):
-the 1080p k_cgs launches with the 252-block geometry (18 x 14 blocks of
+the 1080p k_cgs launches with the 255-block geometry (17 x 15 blocks of
 64 x 4), 76 B per pixel per active launch (launches shorter
 than 15 us returned after the prologue), over the union of their execution
 intervals — the wall time during which at least one fine 1080p CG launch
@@ -24,7 +24,7 @@ def main():
     for r in csv.DictReader(open(path)):
         if not r["Kernel_Name"].replace("void ", "").startswith("k_cgs"):
             continue
-        if (int(r["Grid_Size_X"]), int(r["Grid_Size_Y"])) != (18 * 64, 14 * 4):
+        if (int(r["Grid_Size_X"]), int(r["Grid_Size_Y"])) != (17 * 64, 15 * 4):
             continue
         iv.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"])))
     iv.sort()

@@ -1,14 +1,14 @@
 """How busy the lanes' fine-solve token is in a rocprofv3 kernel trace of the
 default bench (tools/profile.sh's trace_kernel_trace.csv): over the lanes-mode
 steps (from the first side-by-side fine k_cgs launch to the serial pair that
-follows them) (the 252-block lanes geometry: grid
-1152x56 at 1080p, 896x72 at 864x1536), the fraction of time with 0, 1 and 2
+follows them) (the lanes geometry, 17 x 15 and 14 x 18 blocks: grid
+1088x60 at 1080p, 896x72 at 864x1536), the fraction of time with 0, 1 and 2
 of them in flight, and the GPU's overall busy fraction over that span.
 usage: python tools/token_util.py TRACE_CSV"""
 import csv
 import sys
 
-FINE = {("1152", "56"), ("896", "72")}
+FINE = {("1088", "60"), ("896", "72")}
 
 
 def union_len(iv):
@@ -33,10 +33,10 @@ def main():
             fine.append((s, e))
     t0 = min(s for s, _ in fine)
     # the lanes-mode steps (timed, host to host, streamed) end where the
-    # serial per-level pair starts: the first single-solve (504-block)
+    # serial per-level pair starts: the first single-solve (510-block)
     # 1080p launch after them
     single = sorted(int(r["Start_Timestamp"]) for r in rows
-                    if "k_cgs" in r["Kernel_Name"] and (r["Grid_Size_X"], r["Grid_Size_Y"]) == ("1152", "112")
+                    if "k_cgs" in r["Kernel_Name"] and (r["Grid_Size_X"], r["Grid_Size_Y"]) == ("1088", "120")
                     and int(r["Start_Timestamp"]) > t0)
     t1 = single[0] if single else max(e for _, e in fine)
     fine = [(s, min(e, t1)) for s, e in fine if s < t1]
