@@ -190,7 +190,9 @@ int of_set_option(of_ctx *ctx, int option, int value);
 #define OF_OPT_SOR_FALLBACKS 2
 /*   OF_OPT_DEVICE_BYTES   device bytes the context and its batch lanes hold in
  *                         grow-only buffers (arena, SOR sweep ring, gather
- *                         buffer): flat across repeated pairs of one size */
+ *                         buffer): flat across repeated pairs of one size; plus
+ *                         an open point tracker's buffers (of_tracks_open),
+ *                         which leave the count again at of_tracks_close */
 #define OF_OPT_DEVICE_BYTES 4
 /*   OF_OPT_RCCL_NRANKS    ranks of the context's RCCL communicator as RCCL
  *                         reports them (ncclCommCount; 0 before of_rccl_init) */
@@ -432,6 +434,121 @@ int of_estimate_interp(of_ctx *ctx, of_params *params, const float *im1, const f
                        int H, int W, int C, double alpha1, double alpha2, int n, const double *t,
                        float *out, float *out_fw, float *out_bw, uint8_t *out_info,
                        of_stats *stats_fw, of_stats *stats_bw);
+
+/*
+ * Dense point trajectories across a frame sequence (Sundaram, Brox and
+ * Keutzer, ECCV 2010).  A table of tracks: a point is carried from frame to
+ * frame by the forward flow; its track ends where the forward-backward test
+ * or a motion boundary says the flow cannot be trusted, or where it leaves
+ * the frame; new tracks are seeded on a grid wherever the picture has
+ * structure and no live track covers the cell.  A point is (x, y) = (column,
+ * row) in fp32, pixel centres at integers, as for flows (u along columns); the
+ * table stores it as n x 2 floats {x, y}.  Everything in double from the fp32
+ * inputs, no fma contraction, in exactly the order written (a numpy float64
+ * restatement gives the same bits); bil, inside and near as defined above
+ * ("Using a flow on an image").  H * W >= 2^31: OF_ENOTSUP.
+ *
+ * Options.  Any value out of range or not finite: OF_EINVAL, checked on the
+ * host before any launch (every entry checks the whole struct).
+ */
+#define OF_TRACK_ALIVE 0            /* still tracked */
+#define OF_TRACK_OCCLUDED 1         /* the forward-backward test failed */
+#define OF_TRACK_LEFT_FRAME 2       /* left the frame */
+#define OF_TRACK_MOTION_BOUNDARY 3  /* ended at a motion boundary */
+typedef struct of_track_opts {
+  int32_t step;          /* seeding grid: one candidate per step x step cell, 1..64 */
+  int32_t max_tracks;    /* capacity of the track table, 1..2^24 */
+  double alpha1, alpha2; /* forward-backward test, as of_fb_consistency (0.01, 0.5); >= 0 */
+  double beta1, beta2;   /* motion-boundary test (Sundaram et al.: 0.01, 0.002); >= 0 */
+  double min_eig;        /* seeding: smallest eigenvalue threshold, >= 0; 0 accepts every free cell */
+} of_track_opts;
+/*
+ * of_track_advance: one step of n tracks along F = fw (frame k -> k+1) with
+ * B = bw (frame k+1 -> k), planar 2 x H x W.  A track whose status is not 0
+ * comes back as it is.  For an alive track at (x, y):
+ *   xd = x; yd = y
+ *   !inside(yd, xd)                      -> status 2      (also NaN / Inf positions)
+ *   u = bil(F.x, yd, xd); v = bil(F.y, yd, xd)
+ *   x1 = xd + u; y1 = yd + v
+ *   !inside(y1, x1)                      -> status 2      (a NaN flow sample lands here)
+ *   bu = bil(B.x, y1, x1); bv = bil(B.y, y1, x1)
+ *   du = u + bu; dv = v + bv; err = du*du + dv*dv
+ *   thr = alpha1*((u*u + v*v) + (bu*bu + bv*bv)) + alpha2
+ *   !(err <= thr)                        -> status 1
+ *   i = near(yd, H); j = near(xd, W)
+ *   jm = max(j-1, 0); jp = min(j+1, W-1); im = max(i-1, 0); ip = min(i+1, H-1)
+ *   ux = F[i][jp].x - F[i][jm].x; uy = F[ip][j].x - F[im][j].x; vx, vy the same with .y
+ *   g = 0.25*((ux*ux + uy*uy) + (vx*vx + vy*vy))
+ *   !(g <= beta1*(u*u + v*v) + beta2)    -> status 3
+ *   otherwise (x, y) <- ((float)x1, (float)y1), status 0
+ * The tests run in that order, the first that fires decides; a track that ends
+ * keeps its last position; the negated comparisons make NaN end a track.
+ * (float)x1 <= W-1 follows from x1 <= W-1, so an alive track is always inside
+ * the frame.  xy_in / xy_out: n x 2; status_in / status_out: n bytes; n >= 1.
+ */
+int of_track_advance(of_ctx *ctx, const float *fw, const float *bw, int H, int W, const of_track_opts *opts,
+                     int n, const float *xy_in, const uint8_t *status_in, float *xy_out, uint8_t *status_out);
+/*
+ * of_track_seed: new tracks on the gray plane G (H x W fp32) for a table of n
+ * tracks (n may be 0, then xy / status may be NULL; n <= max_tracks).  The
+ * cells are ci < ceil(H/step), cj < ceil(W/step), in row-major order.
+ *   - a cell's candidate pixel is (i, j) = (ci*step + step/2, cj*step + step/2)
+ *     (integer division); a cell whose candidate is outside the frame has none
+ *   - a cell is occupied when some alive track has
+ *     (near(y, H) / step, near(x, W) / step) == (ci, cj)
+ *   - a free cell's candidate is accepted when min_eig == 0, or when, summing
+ *     over the 3 x 3 window (a, b) around (i, j) in row-major order, a and b
+ *     clamped to the frame before use,
+ *       gx = 0.5*(G[a][min(b+1, W-1)] - G[a][max(b-1, 0)]);  gy likewise along rows
+ *       Jxx += gx*gx; Jxy += gx*gy; Jyy += gy*gy
+ *     T = Jxx + Jyy; D = Jxx*Jyy - Jxy*Jxy satisfy
+ *       T >= 2*min_eig && (D - min_eig*T) + min_eig*min_eig >= 0
+ *     (lambda_min(J) >= min_eig without a square root)
+ *   - accepted cells take the ids n, n+1, ... in row-major cell order while
+ *     id < max_tracks (an exclusive prefix sum over the accept flags: the same
+ *     ids whatever the launch geometry); the rest are dropped and counted
+ *   - a new track is at ((float)j, (float)i), status 0, start = frame (>= 0)
+ * *n_new = tracks added, *n_dropped = accepted cells the table had no room
+ * for, xy_new = the n_new new points (room for min(max_tracks - n, cells)).
+ */
+int of_track_seed(of_ctx *ctx, const float *gray, int H, int W, const of_track_opts *opts, int frame,
+                  int n, const float *xy, const uint8_t *status,
+                  int32_t *n_new, int32_t *n_dropped, float *xy_new);
+/*
+ * The tracker session: one per context, its table and frames stay on the
+ * device.  Ids are table indices and never move; dead tracks keep their slot.
+ *   of_tracks_open   frames of H x W x C (C 1 or 3) with the given parameter
+ *                    set; a second open on the context, or an open while a
+ *                    pair stream is open: OF_EINVAL
+ *   of_tracks_push   the next frame.  The first push only seeds (frame index
+ *                    0; the out_* / state_* / stats buffers are untouched).
+ *                    Every later push estimates both flows between the
+ *                    previous frame and this one from a fresh copy of the
+ *                    of_params given at open (out_fw, out_bw, state_fw,
+ *                    state_bw, any of which may be NULL, are bitwise those of
+ *                    of_estimate_flow_bidir on that pair with alpha1 / alpha2
+ *                    of the options; the stats likewise), advances the table
+ *                    along them on the device, seeds on this frame's gray
+ *                    plane with start = this frame's index, and keeps the
+ *                    frame as the previous one.  The gray plane is the frame
+ *                    itself for C = 1 and the _rgb2gray plane of
+ *                    of_preprocess for C = 3.  *n_tracks = the table size
+ *                    after the push; n_new / n_dropped as of_track_seed (all
+ *                    three may be NULL).
+ *   of_tracks_read   tracks first .. first+n-1 (xy n x 2, status, start: the
+ *                    frame index a track was seeded in; any may be NULL)
+ *   of_tracks_close  free the tracker (of_ctx_destroy does it too)
+ * push, read and close without an open tracker: OF_EINVAL.  Other entries of
+ * the context may be called between pushes.  The tracker's buffers are its
+ * own allocations, not arena memory; their bytes are counted in
+ * OF_OPT_DEVICE_BYTES from open to close.
+ */
+int of_tracks_open(of_ctx *ctx, const of_params *params, int H, int W, int C, const of_track_opts *opts);
+int of_tracks_push(of_ctx *ctx, const float *frame, float *out_fw, float *out_bw, uint8_t *state_fw,
+                   uint8_t *state_bw, int32_t *n_tracks, int32_t *n_new, int32_t *n_dropped,
+                   of_stats *stats_fw, of_stats *stats_bw);
+int of_tracks_read(of_ctx *ctx, int first, int n, float *xy, uint8_t *status, int32_t *start);
+int of_tracks_close(of_ctx *ctx);
 
 /* compute_flow_base() for one pyramid level with the given alpha (one call =
  * all warping iterations of the level; hs.py:109-142, ba.py:143-206,

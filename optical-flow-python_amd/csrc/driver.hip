@@ -17,6 +17,7 @@
 //   host_image.hip  image / flow-field helpers, taps, pyramids, ROF, derivatives, medians
 //   host_solve.hip  CG and SOR dispatch, solve log, deferred statistics, gen_* solvers
 //   host_flow.hip   assembly dispatch, token, per-level IRLS loops, schedule, estimate_*
+//   host_track.hip  point tracker: advance and seed steps, stage entries, the session
 //   batch.hip       lanes, of_pairs_run[_host], pair pool, slot copies, RCCL gather
 //   api.hip         context, options, profiling, single-pair and stage entries
 #include <hip/hip_runtime.h>
@@ -39,6 +40,7 @@
 
 #include "kernels_img.hip"
 #include "kernels_flow.hip"
+#include "kernels_track.hip"
 #include "kernels_solve.hip"
 #include "kernels_gen.hip"
 
@@ -46,5 +48,6 @@
 #include "host_image.hip"
 #include "host_solve.hip"
 #include "host_flow.hip"
+#include "host_track.hip"
 #include "batch.hip"
 #include "api.hip"

@@ -163,6 +163,23 @@ struct PairPool {
   OfError err{OF_OK, ""};
 };
 
+// the point tracker of a context (of_tracks_open, host_track.hip): its own
+// device allocations, which outlive the arena's per-call reset
+struct Tracker {
+  int H = 0, W = 0, C = 0;
+  of_params P;        // as given at open; every push starts from a copy
+  of_track_opts opt;
+  int n = 0;                     // tracks in the table
+  int frames = 0;                // frames pushed
+  float *frame[2] = {nullptr, nullptr};  // H x W x C dense; frame[frames & 1] receives the next one
+  float2 *xy = nullptr;                  // the table: max_tracks entries each
+  uint8_t *status = nullptr;
+  int32_t *start = nullptr;
+  uint8_t *occ = nullptr, *flags = nullptr;  // per cell
+  int *bcnt = nullptr;                       // the cell kernels' block counts, then the total
+  size_t bytes = 0;                          // of all of the above
+};
+
 }  // namespace
 
 #define OF_SOLVE_RING 256
@@ -298,6 +315,7 @@ struct of_ctx {
   std::vector<Slot> slots;
   HostStage *hs = nullptr;      // of_pairs_run_host staging (lazily created)
   PairPool *pool = nullptr;     // of_pairs_open streaming batch (lanes of its own)
+  Tracker *trk = nullptr;       // of_tracks_open point tracker
   std::vector<of_ctx *> lanes;  // of_pairs_run pipelines: own stream, arena and solver state
   Token big_own;                // (parent) the big-phase token its lanes share
   Token *big = nullptr;         // (lane) token held through phases of >= big_px pixels

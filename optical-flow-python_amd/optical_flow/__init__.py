@@ -7,6 +7,8 @@ as hand-written HIP kernels for gfx950 in liboptflow.so (include/optflow.h).
 from optical_flow.interface import (estimate_flow, estimate_flow_batch, PairStream, estimate_flow_bidirectional,
                                     BidirectionalFlow, interpolate_frames, INTERP_BLEND, INTERP_FRAME1_ONLY,
                                     INTERP_FRAME2_ONLY, INTERP_NEITHER, INTERP_FILLED)
+from optical_flow.tracking import (advance_points, seed_points, PointTracker, track_points, Trajectories,
+                                   TRACK_ALIVE, TRACK_OCCLUDED, TRACK_LEFT_FRAME, TRACK_MOTION_BOUNDARY)
 from optical_flow.utils.warping import warp_image
 from optical_flow.utils.occlusion import forward_backward_check, FB_CONSISTENT, FB_OCCLUDED, FB_OUT_OF_FRAME
 from optical_flow.io.flo_io import read_flo, write_flo
@@ -18,4 +20,6 @@ from optical_flow.methods.config import load_of_method
 __all__ = ['estimate_flow', 'estimate_flow_batch', 'PairStream', 'read_flo', 'write_flo', 'flow_to_color', 'plot_flow', 'flow_angular_error',
            'load_of_method', 'estimate_flow_bidirectional', 'BidirectionalFlow', 'forward_backward_check',
            'FB_CONSISTENT', 'FB_OCCLUDED', 'FB_OUT_OF_FRAME', 'interpolate_frames', 'warp_image', 'INTERP_BLEND',
-           'INTERP_FRAME1_ONLY', 'INTERP_FRAME2_ONLY', 'INTERP_NEITHER', 'INTERP_FILLED']
+           'INTERP_FRAME1_ONLY', 'INTERP_FRAME2_ONLY', 'INTERP_NEITHER', 'INTERP_FILLED', 'advance_points',
+           'seed_points', 'PointTracker', 'track_points', 'Trajectories', 'TRACK_ALIVE', 'TRACK_OCCLUDED',
+           'TRACK_LEFT_FRAME', 'TRACK_MOTION_BOUNDARY']

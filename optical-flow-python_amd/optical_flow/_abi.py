@@ -122,6 +122,17 @@ class OfSolveRecord(C.Structure):
                 "true_rel": self.true_rel, "est_rel": self.est_rel, "true_rel_out": self.true_rel_out}
 
 
+# point tracker (include/optflow.h, "Dense point trajectories"): track status bytes
+OF_TRACK_ALIVE, OF_TRACK_OCCLUDED, OF_TRACK_LEFT_FRAME, OF_TRACK_MOTION_BOUNDARY = 0, 1, 2, 3
+TRACK_MAX_STEP = 64
+TRACK_MAX_TRACKS = 1 << 24
+
+
+class OfTrackOpts(C.Structure):
+    _fields_ = [("step", C.c_int32), ("max_tracks", C.c_int32), ("alpha1", C.c_double), ("alpha2", C.c_double),
+                ("beta1", C.c_double), ("beta2", C.c_double), ("min_eig", C.c_double)]
+
+
 def penalty(kind, p0=1.0, p1=0.0):
     return OfPenalty(PENALTY[kind], 0, float(p0), float(p1))
 

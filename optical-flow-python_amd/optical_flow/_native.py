@@ -10,8 +10,8 @@ import threading
 
 import numpy as np
 
-from optical_flow._abi import (OfParams, OfStats, OfCgGeometry, OfSolveRecord, OfProgressFn, OF_ABI_VERSION,
-                               OF_EINVAL, OF_ENOTSUP)
+from optical_flow._abi import (OfParams, OfStats, OfCgGeometry, OfSolveRecord, OfProgressFn, OfTrackOpts,
+                               OF_ABI_VERSION, OF_EINVAL, OF_ENOTSUP)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("OPTFLOW_LIB", os.path.join(_HERE, "_lib", "liboptflow.so"))
@@ -25,6 +25,7 @@ _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int)
 _vp = C.c_void_p
 _u8p = C.POINTER(C.c_uint8)
+_i32p = C.POINTER(C.c_int32)
 
 _SIGS = {
     "of_abi_version": ([], C.c_int),
@@ -60,6 +61,15 @@ _SIGS = {
                           _fp, _fp, _u8p], C.c_int),
     "of_estimate_interp": ([_vp, C.POINTER(OfParams), _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double,
                             C.c_int, _dp, _fp, _fp, _fp, _u8p, C.POINTER(OfStats), C.POINTER(OfStats)], C.c_int),
+    "of_track_advance": ([_vp, _fp, _fp, C.c_int, C.c_int, C.POINTER(OfTrackOpts), C.c_int, _fp, _u8p, _fp, _u8p],
+                         C.c_int),
+    "of_track_seed": ([_vp, _fp, C.c_int, C.c_int, C.POINTER(OfTrackOpts), C.c_int, C.c_int, _fp, _u8p, _i32p,
+                       _i32p, _fp], C.c_int),
+    "of_tracks_open": ([_vp, C.POINTER(OfParams), C.c_int, C.c_int, C.c_int, C.POINTER(OfTrackOpts)], C.c_int),
+    "of_tracks_push": ([_vp, _fp, _fp, _fp, _u8p, _u8p, _i32p, _i32p, _i32p, C.POINTER(OfStats),
+                        C.POINTER(OfStats)], C.c_int),
+    "of_tracks_read": ([_vp, C.c_int, C.c_int, _fp, _u8p, _i32p], C.c_int),
+    "of_tracks_close": ([_vp], C.c_int),
     "of_compute_flow_base": ([_vp, C.POINTER(OfParams), _fp, C.c_int, C.c_int, C.c_int, _fp, C.c_int,
                               C.c_double, _fp, _fp], C.c_int),
     "of_alt_ba_flow_base": ([_vp, C.POINTER(OfParams), _fp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, _fp,
