@@ -191,8 +191,9 @@ int of_set_option(of_ctx *ctx, int option, int value);
 /*   OF_OPT_DEVICE_BYTES   device bytes the context and its batch lanes hold in
  *                         grow-only buffers (arena, SOR sweep ring, gather
  *                         buffer): flat across repeated pairs of one size; plus
- *                         an open point tracker's buffers (of_tracks_open),
- *                         which leave the count again at of_tracks_close */
+ *                         an open point tracker's (of_tracks_open) and an open
+ *                         temporal denoiser's (of_denoise_open) buffers, which
+ *                         leave the count again at their close */
 #define OF_OPT_DEVICE_BYTES 4
 /*   OF_OPT_RCCL_NRANKS    ranks of the context's RCCL communicator as RCCL
  *                         reports them (ncclCommCount; 0 before of_rccl_init) */
@@ -549,6 +550,114 @@ int of_tracks_push(of_ctx *ctx, const float *frame, float *out_fw, float *out_bw
                    of_stats *stats_fw, of_stats *stats_bw);
 int of_tracks_read(of_ctx *ctx, int first, int n, float *xy, uint8_t *status, int32_t *start);
 int of_tracks_close(of_ctx *ctx);
+
+/*
+ * Motion-compensated temporal denoising of a frame sequence: a frame is
+ * averaged with its neighbours in time, each warped onto it along a flow and
+ * weighted per pixel by how well its warped patch matches the frame's.  Where
+ * the forward-backward state, the frame border or the photometric difference
+ * says a neighbour does not show the same surface, it is left out.
+ * Everything in double from the fp32 inputs, no fma contraction, in exactly
+ * the order written (a numpy float64 restatement gives the same bits); bil,
+ * inside and near as defined above ("Using a flow on an image"); images
+ * H x W x C interleaved, flows planar 2 x H x W, states H x W bytes in
+ * of_fb_consistency's encoding.  H * W >= 2^31: OF_ENOTSUP.
+ *
+ * of_flow_compose: chain f (frame a -> b) and g (b -> c) into out (a -> c).
+ * state_f / state_g may be NULL (all 0), out_state may be NULL.  For pixel
+ * (i, j), (u, v) = f(i, j):
+ *   u or v not finite, or !inside(i + v, j + u):
+ *     out = f(i, j) unchanged, out_state = 2
+ *   otherwise
+ *     r = i + v; q = j + u
+ *     gu = bil(g.x, r, q); gv = bil(g.y, r, q)
+ *     out = ((float)(u + gu), (float)(v + gv))
+ *     out_state = max(state_f[i][j], state_g[near(r, H)][near(q, W)])
+ * so 2 (left the frame) dominates 1 (inconsistent) dominates 0; a NaN sampled
+ * from g propagates into out.
+ */
+int of_flow_compose(of_ctx *ctx, const float *f, const float *g, int H, int W, const uint8_t *state_f,
+                    const uint8_t *state_g, float *out, uint8_t *out_state);
+/*
+ * Options.  Any value out of range or not finite: OF_EINVAL, checked on the
+ * host before any launch (every entry checks the whole struct).
+ */
+typedef struct of_fuse_opts {
+  int32_t radius;   /* session only: neighbours on each side, 1..2 */
+  int32_t patch;    /* half-size r of the comparison window, 0..3 (window (2r+1)^2) */
+  double sigma;     /* noise standard deviation in image units, finite, > 0 */
+  double strength;  /* rejection scale in units of sigma, finite, > 0 (4) */
+  double alpha1, alpha2; /* session only: forward-backward test, as of_fb_consistency; >= 0 */
+} of_fuse_opts;
+/*
+ * of_fuse_frames: the frame I = center fused with n neighbours N_k along
+ * flows[k] (centre -> neighbour k), states[k] their forward-backward states
+ * (NULL: all 0).  C is 1..4, n is 1..8.  With r = patch,
+ *   two_s2 = 2.0*(sigma*sigma);  h2 = (strength*sigma)*(strength*sigma)
+ * and for neighbour k, ascending, pixel (i, j), (u, v) = flows[k](i, j):
+ *   vis_k(i,j) = u, v finite && inside(i + v, j + u) && state_k(i,j) == 0
+ *   where vis_k:  Wk_c = bil(N_k,c, i + v, j + u)                   for each c
+ *                 D_k(i,j) = sum over c ascending: dd = I_c(i,j) - Wk_c; += dd*dd
+ *   window: S = 0, m = 0; for a = i-r..i+r, inside that b = j-r..j+r (row-major),
+ *           positions outside the frame or with vis_k(a,b) == 0 skipped:
+ *             S += D_k(a,b); m += 1
+ *   !vis_k(i,j): w_k = 0
+ *   otherwise:   d = S/(m*C); e = max(d - two_s2, 0); x = min(e/h2, 1)
+ *                w_k = (1 - x)*(1 - x)
+ * (a Tukey-type weight: exactly 1 while the patch difference is explained by
+ * the noise, exactly 0 from e >= h2 on).  Per pixel
+ *   acc_c = I_c(i,j); wsum = 1.0                    (the frame itself has weight 1)
+ *   k ascending: acc_c += w_k*Wk_c; wsum += w_k
+ *   out_c = (float)(acc_c/wsum); out_weight = (float)wsum
+ * wsum is the effective number of frames averaged, 1..n+1.  The window sum
+ * runs in that fixed order whatever the launch geometry.  The frames are taken
+ * as finite.
+ *   neigh      : n x H x W x C
+ *   flows      : n x 2 x H x W
+ *   states     : n x H x W bytes, or NULL
+ *   out        : H x W x C
+ *   out_weight : H x W, or NULL
+ */
+int of_fuse_frames(of_ctx *ctx, const float *center, int H, int W, int C, int n, const float *neigh,
+                   const float *flows, const uint8_t *states, const of_fuse_opts *opts,
+                   float *out, float *out_weight);
+/*
+ * The denoiser session: one per context; the last 2R+1 frames (R = radius)
+ * and the last 2R adjacent pairs' flows and states stay on the device.
+ *   of_denoise_open   frames of H x W x C (C 1 or 3) with the given parameter
+ *                     set; a second open on the context, or an open while a
+ *                     pair stream is open: OF_EINVAL
+ *   of_denoise_push   frame k = 0, 1, ...  For k > 0 both flows between frame
+ *                     k-1 and this one are estimated from a fresh copy of the
+ *                     of_params given at open and zero initial flows; flows
+ *                     and states are bitwise those of of_estimate_flow_bidir
+ *                     on that pair with alpha1 / alpha2 of the options.  For
+ *                     k >= R frame t = k - R is fused and written to out
+ *                     (H x W x C) and out_weight (H x W or NULL), and
+ *                     *out_index = t; otherwise *out_index = -1 and out is
+ *                     untouched.
+ *   of_denoise_flush  emits the next pending frame from the neighbours that
+ *                     exist; *out_index = -1 when nothing is pending.  After
+ *                     the first flush a push is refused (OF_EINVAL).
+ *   of_denoise_close  free the session (of_ctx_destroy does it too)
+ * push, flush and close without an open session: OF_EINVAL.  Frame t is fused
+ * (of_fuse_frames) with the neighbours at offsets -1, +1, -2, +2, in that
+ * order; offsets outside the clip so far, or beyond R, are skipped; with no
+ * neighbour at all out is the frame itself and the weight 1.  With fw_j /
+ * bw_j / sf_j / sb_j the flows j -> j+1, j+1 -> j and their states of pair
+ * (j, j+1), the neighbours use
+ *   +1: fw_t, sf_t                 -1: bw_{t-1}, sb_{t-1}
+ *   +2: of_flow_compose(fw_t, fw_{t+1}; sf_t, sf_{t+1})
+ *   -2: of_flow_compose(bw_{t-1}, bw_{t-2}; sb_{t-1}, sb_{t-2})
+ * For C = 3 the fusion runs on the RGB frames as pushed.  Other entries of the
+ * context may be called between pushes, and a point tracker may be open beside
+ * the denoiser.  The session's buffers are its own allocations, not arena
+ * memory; their bytes are counted in OF_OPT_DEVICE_BYTES from open to close.
+ */
+int of_denoise_open(of_ctx *ctx, const of_params *params, int H, int W, int C, const of_fuse_opts *opts);
+int of_denoise_push(of_ctx *ctx, const float *frame, float *out, float *out_weight, int32_t *out_index);
+int of_denoise_flush(of_ctx *ctx, float *out, float *out_weight, int32_t *out_index);
+int of_denoise_close(of_ctx *ctx);
 
 /* compute_flow_base() for one pyramid level with the given alpha (one call =
  * all warping iterations of the level; hs.py:109-142, ba.py:143-206,

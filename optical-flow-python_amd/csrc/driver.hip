@@ -18,6 +18,7 @@
 //   host_solve.hip  CG and SOR dispatch, solve log, deferred statistics, gen_* solvers
 //   host_flow.hip   assembly dispatch, token, per-level IRLS loops, schedule, estimate_*
 //   host_track.hip  point tracker: advance and seed steps, stage entries, the session
+//   host_fuse.hip   temporal denoising: flow composition, frame fusion, stage entries, the session
 //   batch.hip       lanes, of_pairs_run[_host], pair pool, slot copies, RCCL gather
 //   api.hip         context, options, profiling, single-pair and stage entries
 #include <hip/hip_runtime.h>
@@ -41,6 +42,7 @@
 #include "kernels_img.hip"
 #include "kernels_flow.hip"
 #include "kernels_track.hip"
+#include "kernels_fuse.hip"
 #include "kernels_solve.hip"
 #include "kernels_gen.hip"
 
@@ -49,5 +51,6 @@
 #include "host_solve.hip"
 #include "host_flow.hip"
 #include "host_track.hip"
+#include "host_fuse.hip"
 #include "batch.hip"
 #include "api.hip"

@@ -180,6 +180,22 @@ struct Tracker {
   size_t bytes = 0;                          // of all of the above
 };
 
+// the temporal denoiser of a context (of_denoise_open, host_fuse.hip): rings
+// of the last 2R+1 frames and of the last 2R adjacent pairs' flows and
+// forward-backward states, its own device allocations like the tracker's
+struct Denoiser {
+  int H = 0, W = 0, C = 0, pitch = 0;
+  of_params P;        // as given at open; every push starts from a copy
+  of_fuse_opts opt;
+  int frames = 0;     // frames pushed
+  int next_out = 0;   // the next frame to emit
+  bool flushed = false;
+  float *frame[5] = {};                    // frame k at k % (2R+1): H x W x C dense
+  float2 *fw[4] = {}, *bw[4] = {};         // pair (j, j+1) at j % 2R: pitched flows j -> j+1 and j+1 -> j
+  uint8_t *sf[4] = {}, *sb[4] = {};        // their forward-backward states, H x W dense
+  size_t bytes = 0;                        // of all of the above
+};
+
 }  // namespace
 
 #define OF_SOLVE_RING 256
@@ -316,6 +332,7 @@ struct of_ctx {
   HostStage *hs = nullptr;      // of_pairs_run_host staging (lazily created)
   PairPool *pool = nullptr;     // of_pairs_open streaming batch (lanes of its own)
   Tracker *trk = nullptr;       // of_tracks_open point tracker
+  Denoiser *den = nullptr;      // of_denoise_open temporal denoiser
   std::vector<of_ctx *> lanes;  // of_pairs_run pipelines: own stream, arena and solver state
   Token big_own;                // (parent) the big-phase token its lanes share
   Token *big = nullptr;         // (lane) token held through phases of >= big_px pixels

@@ -133,6 +133,18 @@ class OfTrackOpts(C.Structure):
                 ("beta1", C.c_double), ("beta2", C.c_double), ("min_eig", C.c_double)]
 
 
+# temporal denoising (include/optflow.h, "Motion-compensated temporal denoising")
+FUSE_MAX_NEIGHBOURS = 8
+FUSE_MAX_CHANNELS = 4
+FUSE_MAX_PATCH = 3
+FUSE_MAX_RADIUS = 2
+
+
+class OfFuseOpts(C.Structure):
+    _fields_ = [("radius", C.c_int32), ("patch", C.c_int32), ("sigma", C.c_double), ("strength", C.c_double),
+                ("alpha1", C.c_double), ("alpha2", C.c_double)]
+
+
 def penalty(kind, p0=1.0, p1=0.0):
     return OfPenalty(PENALTY[kind], 0, float(p0), float(p1))
 

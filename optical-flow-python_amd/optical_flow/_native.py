@@ -10,7 +10,7 @@ import threading
 
 import numpy as np
 
-from optical_flow._abi import (OfParams, OfStats, OfCgGeometry, OfSolveRecord, OfProgressFn, OfTrackOpts,
+from optical_flow._abi import (OfParams, OfStats, OfCgGeometry, OfSolveRecord, OfProgressFn, OfTrackOpts, OfFuseOpts,
                                OF_ABI_VERSION, OF_EINVAL, OF_ENOTSUP)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -70,6 +70,13 @@ _SIGS = {
                         C.POINTER(OfStats)], C.c_int),
     "of_tracks_read": ([_vp, C.c_int, C.c_int, _fp, _u8p, _i32p], C.c_int),
     "of_tracks_close": ([_vp], C.c_int),
+    "of_flow_compose": ([_vp, _fp, _fp, C.c_int, C.c_int, _u8p, _u8p, _fp, _u8p], C.c_int),
+    "of_fuse_frames": ([_vp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _u8p, C.POINTER(OfFuseOpts), _fp,
+                        _fp], C.c_int),
+    "of_denoise_open": ([_vp, C.POINTER(OfParams), C.c_int, C.c_int, C.c_int, C.POINTER(OfFuseOpts)], C.c_int),
+    "of_denoise_push": ([_vp, _fp, _fp, _fp, _i32p], C.c_int),
+    "of_denoise_flush": ([_vp, _fp, _fp, _i32p], C.c_int),
+    "of_denoise_close": ([_vp], C.c_int),
     "of_compute_flow_base": ([_vp, C.POINTER(OfParams), _fp, C.c_int, C.c_int, C.c_int, _fp, C.c_int,
                               C.c_double, _fp, _fp], C.c_int),
     "of_alt_ba_flow_base": ([_vp, C.POINTER(OfParams), _fp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, _fp,

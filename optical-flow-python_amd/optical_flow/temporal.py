@@ -1,0 +1,266 @@
+"""Motion-compensated temporal denoising of a frame sequence: a frame is
+averaged with its neighbours in time, each warped onto it along a flow and
+weighted per pixel by how well its warped patch matches the frame's; what the
+forward-backward masks, the frame border or the photometric difference say
+does not match is left out.  include/optflow.h ("Motion-compensated temporal
+denoising") states the arithmetic; in a session the frames, flows and masks
+stay on the GPU (of_denoise_*), only the denoised frames come back.
+
+Flows are (H, W, 2) with u along columns, as everywhere in the package; masks
+are forward_backward_check's (0 consistent, 1 occluded, 2 out of frame)."""
+import ctypes as C
+
+import numpy as np
+
+from optical_flow import _abi
+from optical_flow import _native as nat
+from optical_flow.methods.config import load_of_method
+from optical_flow.tracking import _frame_size, _i32ptr, _int_in
+
+
+def _number(name, v, positive):
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) \
+            or (v <= 0 if positive else v < 0):
+        raise ValueError(f"{name} must be a finite number {'> 0' if positive else '>= 0'}, got {v!r}")
+    return float(v)
+
+
+def _fuse_opts(sigma, radius=1, strength=4.0, patch=2, alpha1=0.01, alpha2=0.5):
+    """of_fuse_opts from the keyword arguments; ValueError for anything the
+    library would refuse (ranges of include/optflow.h)."""
+    if sigma is None:
+        raise ValueError("sigma (the noise standard deviation in image units) is required")
+    return _abi.OfFuseOpts(_int_in("radius", radius, 1, _abi.FUSE_MAX_RADIUS),
+                           _int_in("patch", patch, 0, _abi.FUSE_MAX_PATCH), _number("sigma", sigma, True),
+                           _number("strength", strength, True), _number("alpha1", alpha1, False),
+                           _number("alpha2", alpha2, False))
+
+
+def _flow(name, f, shape=None):
+    f = np.asarray(f)
+    if f.ndim != 3 or f.shape[2] != 2 or f.dtype.kind not in "fiu" or (shape is not None and f.shape[:2] != shape):
+        want = "(H, W, 2)" if shape is None else f"{shape + (2,)}"
+        raise ValueError(f"{name} must be a {want} array of numbers, got {f.dtype} {f.shape}")
+    return f
+
+
+def _state(name, s, H, W):
+    """A forward-backward mask as contiguous (H, W) uint8, or None."""
+    if s is None:
+        return None
+    s = np.asarray(s)
+    if s.shape != (H, W) or s.dtype.kind not in "iub" or (s.size and (s.min() < 0 or s.max() > 255)):
+        raise ValueError(f"{name} must be ({H}, {W}) integers in 0..255, got {s.dtype} {s.shape}")
+    return np.ascontiguousarray(s, dtype=np.uint8)
+
+
+def _planar32(f):
+    with np.errstate(over='ignore'):
+        return nat.planar(f)
+
+
+def compose_flows(f, g, state_f=None, state_g=None, return_state=False):
+    """Chain the flow `f` (frame a -> b) with `g` (b -> c), both (H, W, 2):
+    returns the flow a -> c, (H, W, 2) float64: f plus g sampled bilinearly
+    where f lands.  Where f is not finite or leaves the frame the result is f
+    itself.  With `return_state` also the (H, W) uint8 mask of the result: 2
+    where f leaves the frame, else the larger of `state_f` at the pixel and
+    `state_g` at the pixel nearest to where f lands (None: all consistent), in
+    forward_backward_check's encoding (of_flow_compose)."""
+    f = _flow("f", f)
+    H, W = f.shape[:2]
+    g = _flow("g", g, (H, W))
+    _frame_size(H, W)
+    sf, sg = _state("state_f", state_f, H, W), _state("state_g", state_g, H, W)
+    out = np.empty((2, H, W), dtype=np.float32)
+    so = np.empty((H, W), dtype=np.uint8) if return_state else None
+    ctx = nat.context()
+    ctx.check(ctx.lib.of_flow_compose(ctx.handle, nat.ptr(_planar32(f)), nat.ptr(_planar32(g)), H, W, nat.u8ptr(sf),
+                                      nat.u8ptr(sg), nat.ptr(out), nat.u8ptr(so)))
+    return (nat.interleaved(out), so) if return_state else nat.interleaved(out)
+
+
+def _frame_stack(center, neighbours):
+    center = np.asarray(center)
+    if center.ndim not in (2, 3) or center.size == 0 or center.dtype.kind not in "fiu":
+        raise ValueError(f"center must be a non-empty (H, W) or (H, W, C) array of numbers, got {center.dtype} "
+                         f"{center.shape}")
+    Cc = 1 if center.ndim == 2 else center.shape[2]
+    if not 1 <= Cc <= _abi.FUSE_MAX_CHANNELS:
+        raise ValueError(f"frames must have 1..{_abi.FUSE_MAX_CHANNELS} channels, got {Cc}")
+    neighbours = [np.asarray(x) for x in neighbours]
+    if not 1 <= len(neighbours) <= _abi.FUSE_MAX_NEIGHBOURS:
+        raise ValueError(f"1..{_abi.FUSE_MAX_NEIGHBOURS} neighbours, got {len(neighbours)}")
+    for x in neighbours:
+        if x.shape != center.shape or x.dtype.kind not in "fiu":
+            raise ValueError(f"every neighbour must be a {center.shape} array of numbers, got {x.dtype} {x.shape}")
+    return center, neighbours, Cc
+
+
+def fuse_frames(center, neighbours, flows, sigma=None, states=None, strength=4.0, patch=2, return_weight=False):
+    """`center`, (H, W) or (H, W, C) with C <= 4, fused with 1..8 `neighbours`
+    of the same shape along `flows` (one (H, W, 2) flow centre -> neighbour
+    each) and, optionally, their forward-backward masks `states` (None, or one
+    (H, W) mask or None per neighbour): returns the fused frame, float64 in
+    center's shape; with `return_weight` also the (H, W) float64 effective
+    number of frames averaged per pixel, 1 .. len(neighbours) + 1.
+
+    A neighbour counts at a pixel where its flow is finite, stays in the frame
+    and its mask is 0; its weight is 1 while the mean squared difference of the
+    (2 patch + 1)^2 window to the warped neighbour is at most 2 sigma^2 (what
+    noise of standard deviation `sigma` explains) and falls to exactly 0 at
+    2 sigma^2 + (strength sigma)^2 (of_fuse_frames).  `sigma` is required."""
+    center, neighbours, Cc = _frame_stack(center, neighbours)
+    H, W = center.shape[:2]
+    _frame_size(H, W)
+    n = len(neighbours)
+    flows = list(flows)
+    if len(flows) != n:
+        raise ValueError(f"{n} neighbours but {len(flows)} flows")
+    flows = [_flow(f"flows[{k}]", f, (H, W)) for k, f in enumerate(flows)]
+    opts = _fuse_opts(sigma, 1, strength, patch)
+    st = None
+    if states is not None:
+        states = list(states)
+        if len(states) != n:
+            raise ValueError(f"{n} neighbours but {len(states)} states")
+        if any(s is not None for s in states):
+            st = np.zeros((n, H, W), dtype=np.uint8)
+            for k, s in enumerate(states):
+                if s is not None:
+                    st[k] = _state(f"states[{k}]", s, H, W)
+    c32 = nat.f32(np.asarray(center, dtype=float))
+    n32 = nat.f32(np.stack([np.asarray(x, dtype=float) for x in neighbours]))
+    f32 = np.ascontiguousarray(np.stack([_planar32(f) for f in flows]))
+    out = np.empty(center.shape, dtype=np.float32)
+    wgt = np.empty((H, W), dtype=np.float32) if return_weight else None
+    ctx = nat.context()
+    ctx.check(ctx.lib.of_fuse_frames(ctx.handle, nat.ptr(c32), H, W, Cc, n, nat.ptr(n32), nat.ptr(f32), nat.u8ptr(st),
+                                     C.byref(opts), nat.ptr(out), nat.ptr(wgt)))
+    out = out.astype(np.float64)
+    return (out, wgt.astype(np.float64)) if return_weight else out
+
+
+class TemporalDenoiser:
+    """Temporal denoiser over frames of one shape, (H, W) or (H, W, 3): the
+    last 2 radius + 1 frames and both flows and masks of the pairs between
+    them stay on the GPU (of_denoise_open / _push / _flush).
+
+        with TemporalDenoiser(frames[0].shape, sigma=10.0) as dn:
+            for f in frames:
+                r = dn.push(f)          # None for the first `radius` frames,
+                ...                     # then (index, frame) of frame index
+            for index, frame in dn.flush():
+                ...                     # the last `radius` frames
+
+    Frame t is fused (fuse_frames) with frames t - radius .. t + radius that
+    exist, along the flows of estimate_flow_bidirectional(frame k, frame k+1,
+    method, params, alpha1, alpha2) on the adjacent pairs and their masks;
+    two frames apart the flows are chained (compose_flows).  Frames come back
+    as float64 in the input's shape; `last_weight` holds the (H, W) float64
+    effective number of frames averaged in the frame returned last.  One
+    denoiser per context: by default the calling thread's context (other
+    calls of the package may run between pushes), or a `context`
+    (_native.Context) of your own.  `sigma` is required."""
+
+    def __init__(self, shape, method='classic+nl-fast', params=None, sigma=None, radius=1, strength=4.0, patch=2,
+                 alpha1=0.01, alpha2=0.5, context=None):
+        self._ctx = None
+        shape = tuple(int(s) for s in shape)
+        if len(shape) not in (2, 3) or (len(shape) == 3 and shape[2] != 3):
+            raise ValueError(f"shape must be (H, W) or (H, W, 3), got {shape}")
+        H, W = shape[:2]
+        _frame_size(H, W)
+        self._opts = _fuse_opts(sigma, radius, strength, patch, alpha1, alpha2)
+        ope = load_of_method(method)
+        if params is not None:
+            ope.parse_input_parameter(params)
+        P = ope.to_params()
+        P.guide_mode = int(ope._METHOD == 'classic_nl' and ope.color_images is not None)
+        self.shape, self.H, self.W, self.channels = shape, H, W, 3 if len(shape) == 3 else 1
+        self.radius = self._opts.radius
+        self.frames = 0
+        self.last_weight = None
+        ctx = nat.context() if context is None else context
+        ctx.check(ctx.lib.of_denoise_open(ctx.handle, C.byref(P), H, W, self.channels, C.byref(self._opts)))
+        self._ctx = ctx
+
+    def _result(self, out, wgt, idx):
+        if idx[0] < 0:
+            return None
+        self.last_weight = wgt.astype(np.float64)
+        return int(idx[0]), out.astype(np.float64)
+
+    def push(self, frame):
+        """The next frame.  Returns (index, frame) of the denoised frame that
+        became complete, float64 in the input's shape, or None while fewer
+        than radius + 1 frames have been pushed."""
+        if self._ctx is None:
+            raise ValueError("the denoiser is closed")
+        f = np.asarray(frame)
+        if f.shape != self.shape or f.dtype.kind not in "fiu":
+            raise ValueError(f"frames must be {self.shape} arrays of numbers, got {f.dtype} {f.shape}")
+        f = nat.f32(np.asarray(f, dtype=float))
+        out = np.empty(self.shape, dtype=np.float32)
+        wgt = np.empty((self.H, self.W), dtype=np.float32)
+        idx = np.full(1, -1, dtype=np.int32)
+        ctx = self._ctx
+        ctx.check(ctx.lib.of_denoise_push(ctx.handle, nat.ptr(f), nat.ptr(out), nat.ptr(wgt), _i32ptr(idx)))
+        self.frames += 1
+        return self._result(out, wgt, idx)
+
+    def flush(self):
+        """Yields (index, frame) for the frames still pending at the end of
+        the clip, fused with the neighbours that exist.  No push after it."""
+        if self._ctx is None:
+            raise ValueError("the denoiser is closed")
+        ctx = self._ctx
+        while True:
+            out = np.empty(self.shape, dtype=np.float32)
+            wgt = np.empty((self.H, self.W), dtype=np.float32)
+            idx = np.full(1, -1, dtype=np.int32)
+            ctx.check(ctx.lib.of_denoise_flush(ctx.handle, nat.ptr(out), nat.ptr(wgt), _i32ptr(idx)))
+            r = self._result(out, wgt, idx)
+            if r is None:
+                return
+            yield r
+
+    def close(self):
+        if self._ctx is not None:
+            ctx, self._ctx = self._ctx, None
+            if ctx.handle:
+                ctx.check(ctx.lib.of_denoise_close(ctx.handle))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def denoise_frames(frames, method='classic+nl-fast', sigma=None, radius=1, strength=4.0, patch=2, alpha1=0.01,
+                   alpha2=0.5, params=None, return_weight=False):
+    """Denoise `frames` (a sequence of at least one (H, W) or (H, W, 3) frame
+    of one shape) with a TemporalDenoiser: returns (T, H, W[, 3]) float64;
+    with `return_weight` also the (T, H, W) float64 effective number of frames
+    averaged per pixel.  `sigma` is required."""
+    frames = [np.asarray(f) for f in frames]
+    if not frames or any(f.shape != frames[0].shape for f in frames):
+        raise ValueError("frames must be a non-empty sequence of frames of one shape")
+    out = np.empty((len(frames),) + frames[0].shape, dtype=np.float64)
+    wgt = np.empty((len(frames),) + frames[0].shape[:2], dtype=np.float64)
+    with TemporalDenoiser(frames[0].shape, method, params, sigma, radius, strength, patch, alpha1, alpha2) as dn:
+        def take(r):
+            if r is not None:
+                out[r[0]], wgt[r[0]] = r[1], dn.last_weight
+        for f in frames:
+            take(dn.push(f))
+        for r in dn.flush():
+            take(r)
+    return (out, wgt) if return_weight else out
