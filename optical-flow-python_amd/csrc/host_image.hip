@@ -171,10 +171,16 @@ void correlate_sep(of_ctx *c, const Img &in, const Img &out, const Taps &tx, con
   correlate(c, tmp, out, ty);
 }
 
+// k_resize takes its source coordinates in 32-bit integers (resize_src)
+void resize_fits(int H, int W, int nH, int nW) {
+  REQUIRE(2LL * H * nH < (1LL << 31) && 2LL * W * nW < (1LL << 31), OF_ENOTSUP, "resize of a plane this large");
+}
+
 // the smoothed level `sm` resized by `ratio`
 Img resize_img(of_ctx *c, const Img &sm, double ratio) {
   int nH, nW;
   resize_dims(sm.H, sm.W, ratio, &nH, &nW);
+  resize_fits(sm.H, sm.W, nH, nW);
   Img out = new_img(c, nH, nW, sm.C);
   Grid2 g = grid2(nH, nW);
   launch(c, "resize", k_resize<float>, gz(g, sm.C), g.block, 0, (const float *)sm.p, sm.H, sm.W, sm.P, sm.ps(),
@@ -340,6 +346,7 @@ void wmf(of_ctx *c, const F2 &uv, const Img &guide, const float *occ, const F2 &
 
 void resample_f2(of_ctx *c, const F2 &in, const F2 &out) {
   const float ratio = (float)((double)out.H / (double)in.H);
+  resize_fits(in.H, in.W, out.H, out.W);
   Grid2 g = grid2(out.H, out.W);
   launch(c, "resample_flow", k_resize<float2>, g.grid, g.block, 0, (const float2 *)in.p, in.H, in.W, in.P,
          (size_t)in.H * in.P, out.p, out.H, out.W, out.P, (size_t)out.H * out.P, ratio);

@@ -78,6 +78,16 @@ __device__ __forceinline__ float q_u8(float x) {
   return fminf(fmaxf(q, 0.0f), 255.0f);
 }
 
+// double(rgb2gray(uint8(.))) of one pixel (interface.py:74-88) in the
+// reference's own float64, product by product: (2989 R + 5870 G + 1140 B) /
+// 10000 lands exactly on k + 0.5 for about one pixel in 10^4, and which way
+// floor(. + 0.5) then goes is decided by float64's rounding of the three
+// products -- float32 went the other way on a third of those pixels
+__device__ __forceinline__ float gray_u8(float r, float g, float b) {
+#pragma clang fp contract(off)
+  return (float)floor(0.2989 * (double)q_u8(r) + 0.5870 * (double)q_u8(g) + 0.1140 * (double)q_u8(b) + 0.5);
+}
+
 // gray (uint8 round trip) of both frames; Lab of frame 1 when lab != nullptr
 template <typename TI>
 __global__ void k_rgb_prep(const TI *__restrict__ rgb1, const TI *__restrict__ rgb2, int H, int W, int C,
@@ -94,8 +104,8 @@ __global__ void k_rgb_prep(const TI *__restrict__ rgb1, const TI *__restrict__ r
     }
     const TI *a = rgb1 + 3 * k, *b = rgb2 + 3 * k;
     const float a0 = (float)a[0], a1 = (float)a[1], a2 = (float)a[2];
-    gray[o] = floorf(0.2989f * q_u8(a0) + 0.5870f * q_u8(a1) + 0.1140f * q_u8(a2) + 0.5f);
-    gray[ps + o] = floorf(0.2989f * q_u8((float)b[0]) + 0.5870f * q_u8((float)b[1]) + 0.1140f * q_u8((float)b[2]) + 0.5f);
+    gray[o] = gray_u8(a0, a1, a2);
+    gray[ps + o] = gray_u8((float)b[0], (float)b[1], (float)b[2]);
     if (!lab) continue;
     float R = a0, G = a1, B = a2;
     if (norm) { R /= 255.0f; G /= 255.0f; B /= 255.0f; }
@@ -276,23 +286,30 @@ __global__ __launch_bounds__(OF_BX *OF_BY) void k_correlate_k(const float *__res
 
 // _matlab_imresize_bilinear / resample_flow: source coordinate
 // (o + 0.5) * (H / nH) - 0.5 clipped to [0, H-1], bilinear, times `mult`.
+// The coordinate is the rational ((2 o + 1) n - nn) / (2 nn): its floor and
+// remainder are taken in integers and only the fraction is rounded (once).
+// In float32 the coordinate itself carried ~n * 2^-24 px of rounding, which a
+// rough field turned into 8.5e-5 px of flow at 113 -> 180 rows.  32-bit:
+// 2 n nn < 2^31 (host-checked, resize_fits).
+__device__ __forceinline__ void resize_src(int o, int n, int nn, int &i0, int &i1, float &f) {
+  const int den = 2 * nn;
+  const int num = min(max((2 * o + 1) * n - nn, 0), (n - 1) * den);
+  i0 = num / den;
+  f = (float)(num - i0 * den) / (float)den;
+  i1 = min(i0 + 1, n - 1);
+}
 template <typename T>
 __global__ void k_resize(const T *__restrict__ in, int H, int W, int P, size_t ps, T *__restrict__ out, int nH, int nW,
                          int nP, size_t nps, float mult) {
   in += blockIdx.z * ps;
   out += blockIdx.z * nps;
-  const float sy = (float)H / (float)nH, sx = (float)W / (float)nW;
   const int j = blockIdx.x * OF_BX + threadIdx.x;
   if (j >= nW) return;
-  float c = fminf(fmaxf((j + 0.5f) * sx - 0.5f, 0.0f), (float)(W - 1));
-  int j0 = (int)floorf(c);
-  float fc = c - j0;
-  int j1 = min(j0 + 1, W - 1);
+  int j0, j1, i0, i1;
+  float fc, fr;
+  resize_src(j, W, nW, j0, j1, fc);
   for (int o = blockIdx.y * OF_BY + threadIdx.y; o < nH; o += gridDim.y * OF_BY) {
-    float r = fminf(fmaxf((o + 0.5f) * sy - 0.5f, 0.0f), (float)(H - 1));
-    int i0 = (int)floorf(r);
-    float fr = r - i0;
-    int i1 = min(i0 + 1, H - 1);
+    resize_src(o, H, nH, i0, i1, fr);
     const T *r0 = in + (size_t)i0 * P, *r1 = in + (size_t)i1 * P;
     T v = (1.0f - fr) * ((1.0f - fc) * r0[j0] + fc * r0[j1]) + fr * ((1.0f - fc) * r1[j0] + fc * r1[j1]);
     out[(size_t)o * nP + j] = mult * v;

@@ -377,6 +377,9 @@ def test_median_filter(golden):
     np.testing.assert_allclose(median_filter2(d["a"], 5), d["a_med"], atol=1e-6)
     np.testing.assert_allclose(median_filter2(d["t"], 5), d["t_med"], atol=1e-6)
     np.testing.assert_allclose(median_filter2(d["a"], 3), d["a3"], atol=1e-6)
+    # size 7 (k_median1<7>): the fixture has no size-7 plane, scipy is the reference's filter
+    from scipy.ndimage import median_filter
+    np.testing.assert_allclose(median_filter2(d["a"], 7), median_filter(d["a"], size=7, mode="reflect"), atol=1e-6)
 
 
 def _spd_flow_system(H, W, seed):
