@@ -192,8 +192,9 @@ int of_set_option(of_ctx *ctx, int option, int value);
  *                         grow-only buffers (arena, SOR sweep ring, gather
  *                         buffer): flat across repeated pairs of one size; plus
  *                         an open point tracker's (of_tracks_open) and an open
- *                         temporal denoiser's (of_denoise_open) buffers, which
- *                         leave the count again at their close */
+ *                         temporal denoiser's (of_denoise_open) and an open
+ *                         stabiliser's (of_stab_open) buffers, which leave the
+ *                         count again at their close */
 #define OF_OPT_DEVICE_BYTES 4
 /*   OF_OPT_RCCL_NRANKS    ranks of the context's RCCL communicator as RCCL
  *                         reports them (ncclCommCount; 0 before of_rccl_init) */
@@ -658,6 +659,179 @@ int of_denoise_open(of_ctx *ctx, const of_params *params, int H, int W, int C, c
 int of_denoise_push(of_ctx *ctx, const float *frame, float *out, float *out_weight, int32_t *out_index);
 int of_denoise_flush(of_ctx *ctx, float *out, float *out_weight, int32_t *out_index);
 int of_denoise_close(of_ctx *ctx);
+
+/*
+ * Global motion estimation and video stabilisation.  The dominant (camera)
+ * motion of a flow field is fitted as a translation, a similarity or an
+ * affine map by iteratively reweighted least squares with Tukey's biweight
+ * and a decreasing cutoff (Odobez and Bouthemy 1995); a stabiliser smooths
+ * the chain of those motions over a clip and warps every frame onto the
+ * smoothed path.  Everything in double from the fp32 inputs, no fma
+ * contraction, in exactly the order written (a numpy float64 restatement gives
+ * the same bits); bil and inside as defined above ("Using a flow on an
+ * image"); min(a, b) is a < b ? a : b and max(a, b) is b > a ? b : a, so a
+ * NaN second operand gives the first.  H * W >= 2^31: OF_ENOTSUP.
+ *
+ * Coordinates and models.  s = 0.5*max(H, W), cx = 0.5*(W-1), cy = 0.5*(H-1);
+ * pixel (i, j) has x = (j - cx)/s, y = (i - cy)/s, and the model flow is
+ *   uh = th0 + th1*x + th2*y;  vh = th3 + th4*x + th5*y
+ * with th1 = th2 = th4 = th5 = 0 (translation), th1 = th5 = a and
+ * th4 = -th2 = b (similarity), or all six free (affine).
+ *
+ * Weight of pixel (i, j) in pass k.  w0 = weight[i][j] (NULL: 1.0), forced to
+ * 0 where u or v is not finite or state[i][j] != 0 (NULL: all 0); there
+ * u = v = 0 is used, so no NaN enters a sum.  With th of the previous pass
+ * (zero for pass 0):
+ *   ru = u - uh; rv = v - vh; r2 = ru*ru + rv*rv
+ *   pass 0:      w = w0
+ *   pass k >= 1: t = min(r2/c2, 1.0); w = w0*((1 - t)*(1 - t))
+ * Sums of a pass, every product formed left to right as written:
+ *   Sw = sum w;  Sx = sum w*x;  Sy = sum w*y
+ *   Sxx = sum (w*x)*x;  Sxy = sum (w*x)*y;  Syy = sum (w*y)*y
+ *   Su = sum w*u;  Sxu = sum (w*x)*u;  Syu = sum (w*y)*u;  Sv, Sxv, Syv with v
+ *   Sr = sum w*r2
+ * Order of every sum, whatever the launch geometry: tiles of 8 rows x 64
+ * columns in row-major tile order, positions outside the frame contributing
+ * +0.0; column l of a tile adds its 8 rows ascending into an accumulator
+ * starting at +0.0; the 64 column values are combined by the halving tree
+ *   for d = 32, 16, ..., 1: s[l] = s[l] + s[l+d] for l < d
+ * the tile values, in tile order, are zero-padded to a multiple of 64 and each
+ * group of 64 is reduced by the same tree, and so on until one value is left.
+ *
+ * Solve of a pass.  !(Sw > 0): th and c2 keep their values, no further pass
+ * solves (the fit stops) and degenerate |= 2.  Otherwise
+ *   translation: th0 = Su/Sw; th3 = Sv/Sw
+ *   similarity:  q = Sxx + Syy; D = q - (Sx*Sx + Sy*Sy)/Sw
+ *                a = ((Sxu + Syv) - (Sx*Su + Sy*Sv)/Sw)/D
+ *                b = ((Sxv - Syu) - (Sx*Sv - Sy*Su)/Sw)/D
+ *                th0 = (Su - a*Sx + b*Sy)/Sw; th3 = (Sv - b*Sx - a*Sy)/Sw
+ *   affine:      m = Sx/Sw; n = Sy/Sw; A = Sxx - m*Sx; B = Sxy - m*Sy
+ *                Cc = Syy - n*Sy; l = B/A; E = Cc - l*B
+ *                per component f in {u, v}:
+ *                  gx = Sxf - m*Sf; gy = Syf - n*Sf; p2 = (gy - l*gx)/E
+ *                  p1 = (gx - B*p2)/A; p0 = (Sf - Sx*p1 - Sy*p2)/Sw
+ *                (th0, th1, th2) = p of u; (th3, th4, th5) = p of v
+ * Rank loss, !(D > 1e-9*Sw), or !(A > 1e-9*Sw) or !(E > 1e-9*Sw): that pass
+ * solves the translation model instead and degenerate |= 1.
+ * Cutoff, starting at c2 = c_min*c_min: after pass 0
+ *   c2 = max(c_min*c_min, (kappa*kappa)*(Sr/Sw))
+ * (th was zero: the weighted mean square of the flow itself), after each later
+ * pass c2 = max(c_min*c_min, c2*decay).  Pass 0 and `iters` robust passes
+ * solve; then one more pass weighs with the final th and c2 as a pass k >= 1,
+ * writes the inlier plane (float)w and does not solve: its sums give
+ * support = Sw and rms = sqrt(Sr/Sw).  passes = the solving passes run (the
+ * one that stopped the fit included); cutoff = sqrt(c2).
+ * The matrix (row-major 2 x 3) maps a point (column, row) of the flow's first
+ * frame to the second:
+ *   M = [1 + th1/s, th2/s, th0 - (th1*cx + th2*cy)/s;
+ *        th4/s, 1 + th5/s, th3 - (th4*cx + th5*cy)/s]
+ * Flows of +-1e30 are finite and enter the sums as they are.
+ * Known limitation: the fit finds the dominant motion.  With the affine model
+ * it breaks down when one coherent foreground region covers roughly 40 % or
+ * more of the frame (it locks onto the wrong layer); the similarity model
+ * held in the same scenes.
+ */
+#define OF_MOTION_TRANSLATION 0
+#define OF_MOTION_SIMILARITY 1
+#define OF_MOTION_AFFINE 2
+/* Any value out of range or not finite: OF_EINVAL, checked on the host before
+ * any launch. */
+typedef struct of_motion_opts {
+  int32_t model;   /* OF_MOTION_*, 0..2 */
+  int32_t iters;   /* robust passes after pass 0, 0..64 (10) */
+  double kappa;    /* first cutoff in units of the flow's rms, > 0 (2) */
+  double decay;    /* factor on c2 per pass, 0 < decay <= 1 (0.5) */
+  double c_min;    /* smallest cutoff in pixels, > 0 (0.5) */
+} of_motion_opts;
+typedef struct of_motion_fit {
+  double theta[6];
+  double matrix[6];
+  double cutoff;    /* sqrt of the final c2, pixels */
+  double support;   /* Sw of the last pass */
+  double rms;       /* sqrt(Sr/Sw) of the last pass (NaN without support) */
+  int32_t passes;
+  int32_t degenerate;  /* 1 rank loss | 2 no support */
+} of_motion_fit;
+/*
+ *   uv         : planar 2 x H x W
+ *   weight     : H x W fp32, every value finite and >= 0 (else OF_EINVAL), or NULL
+ *   state      : H x W bytes (of_fb_consistency's encoding; != 0 masks), or NULL
+ *   out_inlier : H x W fp32, the last pass's w, or NULL
+ */
+int of_fit_motion(of_ctx *ctx, const float *uv, int H, int W, const float *weight, const uint8_t *state,
+                  const of_motion_opts *opts, of_motion_fit *out, float *out_inlier);
+/*
+ * of_warp_affine: A (row-major 2 x 3) maps an output pixel to its source
+ * position.  For output pixel (i, j):
+ *   q = (A[0]*j + A[1]*i) + A[2];  r = (A[3]*j + A[4]*i) + A[5]
+ *   q and r finite and inside(r, q): out(i, j, c) = (float)bil(im_c, r, q), valid 1
+ *   otherwise: out 0, valid 0
+ * im, out: H x W x C interleaved, C is 1..4; valid: H x W bytes or NULL.
+ */
+int of_warp_affine(of_ctx *ctx, const float *im, int H, int W, int C, const double A[6], float *out,
+                   uint8_t *valid);
+/*
+ * The stabiliser session: one per context; the last radius + 1 frames stay on
+ * the device, the motions (six doubles each) on the host.
+ *   of_stab_open   frames of H x W x C (C 1 or 3) with the given parameter set;
+ *                  a second open on the context, or an open while a pair
+ *                  stream is open: OF_EINVAL
+ *   of_stab_push   frame k = 0, 1, ...  For k > 0 both flows between frame k-1
+ *                  and this one are estimated from a fresh copy of the
+ *                  of_params given at open and zero initial flows (bitwise
+ *                  of_estimate_flow_bidir with alpha1 / alpha2 of the options),
+ *                  and M_{k-1} = the matrix of of_fit_motion on the
+ *                  device-resident forward flow with the forward state as
+ *                  `state`, no weight and `fit` of the options.  A motion
+ *                  that cannot be inverted (below) is replaced by the identity.
+ *                  out_motion (6 doubles or NULL) receives M_{k-1} as kept,
+ *                  *degenerate the fit's flags | 4 for every replacement by
+ *                  the identity in this call.  For k >= radius frame
+ *                  t = k - radius is emitted: out (H x W x C), out_valid (H x W
+ *                  bytes or NULL), out_transform (S_t, 6 doubles, or NULL) and
+ *                  *out_index = t; otherwise *out_index = -1 and they are
+ *                  untouched.
+ *   of_stab_flush  emits the next pending frame from the neighbours that
+ *                  exist; *out_index = -1 when nothing is pending.  After the
+ *                  first flush a push is refused (OF_EINVAL).
+ *   of_stab_close  free the session (of_ctx_destroy does it too)
+ * push, flush and close without an open session: OF_EINVAL.  Other entries of
+ * the context may be called between pushes, and a point tracker and a temporal
+ * denoiser may be open beside the stabiliser.  The session's buffers are its
+ * own allocations, not arena memory; their bytes are counted in
+ * OF_OPT_DEVICE_BYTES from open to close.
+ *
+ * Path smoothing, on the host, in double, in the order written.
+ *   inverse of [a b tx; c d ty]:
+ *     det = a*d - b*c; ia = d/det; ib = -b/det; ic = -c/det; id = a/det
+ *     itx = -(ia*tx + ib*ty); ity = -(ic*tx + id*ty)
+ *     !(fabs(det) >= 1e-12) or an entry that is not finite: the matrix is
+ *     replaced by the identity (and so is its inverse), degenerate |= 4
+ *   composition X o Y (Y first), each entry left to right:
+ *     [X0*Y0 + X1*Y3, X0*Y1 + X1*Y4, (X0*Y2 + X1*Y5) + X2;
+ *      X3*Y0 + X4*Y3, X3*Y1 + X4*Y4, (X3*Y2 + X4*Y5) + X5]
+ *   P(t->t) = I;  P(t->t+d) = M_{t+d-1} o P(t->t+d-1)
+ *   P(t->t-d) = inv(M_{t-d}) o P(t->t-d+1)
+ *   g_d = exp(-(d*d)/((2*sigma_t)*sigma_t))
+ *   S_t = (sum g_d*P(t->t+d)) / (sum g_d), entrywise, both sums starting at 0
+ *         and d running 0, -1, +1, -2, +2, ... over the offsets inside the
+ *         clip so far and within the radius
+ * The emitted frame is of_warp_affine(frame t, inv(S_t)): the frame as seen
+ * from the smoothed camera path.
+ */
+typedef struct of_stab_opts {
+  of_motion_opts fit;
+  int32_t radius;        /* frames of the smoothing window on each side, 1..30 */
+  int32_t pad_;
+  double sigma_t;        /* standard deviation of the smoothing window in frames, finite, > 0 */
+  double alpha1, alpha2; /* forward-backward test, as of_fb_consistency; >= 0 */
+} of_stab_opts;
+int of_stab_open(of_ctx *ctx, const of_params *params, int H, int W, int C, const of_stab_opts *opts);
+int of_stab_push(of_ctx *ctx, const float *frame, float *out, uint8_t *out_valid, double *out_transform,
+                 double *out_motion, int32_t *degenerate, int32_t *out_index);
+int of_stab_flush(of_ctx *ctx, float *out, uint8_t *out_valid, double *out_transform, int32_t *degenerate,
+                  int32_t *out_index);
+int of_stab_close(of_ctx *ctx);
 
 /* compute_flow_base() for one pyramid level with the given alpha (one call =
  * all warping iterations of the level; hs.py:109-142, ba.py:143-206,

@@ -70,6 +70,7 @@ int of_ctx_destroy(of_ctx *c) {
   if (c->pool) of_pairs_close(c);
   tracker_free(c);
   denoiser_free(c);
+  stabilizer_free(c);
   for (of_ctx *l : c->lanes) of_ctx_destroy(l);
   c->lanes.clear();
   hipSetDevice(c->device);
@@ -170,7 +171,7 @@ int of_get_option(of_ctx *c, int option, int64_t *value) {
     case OF_OPT_DEVICE_BYTES: {
       // grow-only device buffers of the context and its lanes: the arena
       // chunks, the pipelined SOR's sweep ring and the RCCL gather buffer;
-      // and an open point tracker's and an open temporal denoiser's buffers
+      // and an open point tracker's, temporal denoiser's and stabiliser's buffers
       auto held = [](const of_ctx *x) {
         return (int64_t)(x->arena.reserved() + x->sor_ring_cap + x->gather_cap);
       };
@@ -178,6 +179,7 @@ int of_get_option(of_ctx *c, int option, int64_t *value) {
       for (of_ctx *l : c->lanes) n += held(l);
       if (c->trk) n += (int64_t)c->trk->bytes;
       if (c->den) n += (int64_t)c->den->bytes;
+      if (c->stab) n += (int64_t)c->stab->bytes;
       *value = n;
       return OF_OK;
     }

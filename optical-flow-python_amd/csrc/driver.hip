@@ -19,6 +19,7 @@
 //   host_flow.hip   assembly dispatch, token, per-level IRLS loops, schedule, estimate_*
 //   host_track.hip  point tracker: advance and seed steps, stage entries, the session
 //   host_fuse.hip   temporal denoising: flow composition, frame fusion, stage entries, the session
+//   host_motion.hip global motion: the robust parametric fit, the affine warp, path smoothing, the stabiliser session
 //   batch.hip       lanes, of_pairs_run[_host], pair pool, slot copies, RCCL gather
 //   api.hip         context, options, profiling, single-pair and stage entries
 #include <hip/hip_runtime.h>
@@ -43,6 +44,7 @@
 #include "kernels_flow.hip"
 #include "kernels_track.hip"
 #include "kernels_fuse.hip"
+#include "kernels_motion.hip"
 #include "kernels_solve.hip"
 #include "kernels_gen.hip"
 
@@ -52,5 +54,6 @@
 #include "host_flow.hip"
 #include "host_track.hip"
 #include "host_fuse.hip"
+#include "host_motion.hip"
 #include "batch.hip"
 #include "api.hip"

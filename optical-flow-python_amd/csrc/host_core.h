@@ -196,6 +196,25 @@ struct Denoiser {
   size_t bytes = 0;                        // of all of the above
 };
 
+// the stabiliser of a context (of_stab_open, host_motion.hip): a ring of the
+// last R+1 frames, its own device allocations like the tracker's; the motions
+// between adjacent frames live on the host
+struct Mat6 {
+  double a[6];
+};
+struct Stabilizer {
+  int H = 0, W = 0, C = 0;
+  of_params P;        // as given at open; every push starts from a copy
+  of_stab_opts opt;
+  int frames = 0;     // frames pushed
+  int next_out = 0;   // the next frame to emit
+  bool flushed = false;
+  std::vector<float *> frame;  // frame k at k % (R+1): H x W x C dense
+  std::deque<Mat6> motion;     // M_k at k - motion0, as kept (the identity where the fit's could not be inverted)
+  int motion0 = 0;
+  size_t bytes = 0;            // of the frames
+};
+
 }  // namespace
 
 #define OF_SOLVE_RING 256
@@ -333,6 +352,7 @@ struct of_ctx {
   PairPool *pool = nullptr;     // of_pairs_open streaming batch (lanes of its own)
   Tracker *trk = nullptr;       // of_tracks_open point tracker
   Denoiser *den = nullptr;      // of_denoise_open temporal denoiser
+  Stabilizer *stab = nullptr;   // of_stab_open stabiliser
   std::vector<of_ctx *> lanes;  // of_pairs_run pipelines: own stream, arena and solver state
   Token big_own;                // (parent) the big-phase token its lanes share
   Token *big = nullptr;         // (lane) token held through phases of >= big_px pixels

@@ -1,0 +1,336 @@
+// host_motion.hip — host side of the global motion estimation
+// (kernels_motion.hip): option checks, the robust parametric fit as one chain
+// of launches on a device-resident flow, the affine warp, the path smoothing
+// (host arithmetic on 2 x 3 matrices), the two stage entries on host buffers
+// and the per-context stabiliser session.
+namespace {
+
+void check_motion_opts(const of_motion_opts *o) {
+  REQUIRE(o, OF_EINVAL, "no motion options");
+  REQUIRE(o->model >= OF_MOTION_TRANSLATION && o->model <= OF_MOTION_AFFINE, OF_EINVAL,
+          "motion model must be 0 (translation), 1 (similarity) or 2 (affine)");
+  REQUIRE(o->iters >= 0 && o->iters <= 64, OF_EINVAL, "motion iters must be 0..64");
+  REQUIRE(std::isfinite(o->kappa) && o->kappa > 0, OF_EINVAL, "kappa must be finite and > 0");
+  REQUIRE(std::isfinite(o->decay) && o->decay > 0 && o->decay <= 1, OF_EINVAL, "decay must be in (0, 1]");
+  REQUIRE(std::isfinite(o->c_min) && o->c_min > 0, OF_EINVAL, "c_min must be finite and > 0");
+}
+void check_stab_opts(const of_stab_opts *o) {
+  REQUIRE(o, OF_EINVAL, "no stabiliser options");
+  check_motion_opts(&o->fit);
+  REQUIRE(o->radius >= 1 && o->radius <= 30, OF_EINVAL, "stabiliser radius must be 1..30");
+  REQUIRE(std::isfinite(o->sigma_t) && o->sigma_t > 0, OF_EINVAL, "sigma_t must be finite and > 0");
+  REQUIRE(std::isfinite(o->alpha1) && std::isfinite(o->alpha2) && o->alpha1 >= 0 && o->alpha2 >= 0, OF_EINVAL,
+          "alpha1 and alpha2 must be finite and >= 0");
+}
+void check_motion_frame(int H, int W) {
+  REQUIRE(H > 0 && W > 0, OF_EINVAL, "bad arguments");
+  REQUIRE((size_t)H * W < ((size_t)1 << 31), OF_ENOTSUP, "global motion takes H * W < 2^31");
+}
+
+// th in normalised coordinates -> the pixel-coordinate matrix
+void motion_matrix(const double *th, const MotionFrame &fr, double *M) {
+  OF_NOCONTRACT
+  const double s = fr.s;
+  M[0] = 1.0 + th[1] / s;
+  M[1] = th[2] / s;
+  M[2] = th[0] - (th[1] * fr.cx + th[2] * fr.cy) / s;
+  M[3] = th[4] / s;
+  M[4] = 1.0 + th[5] / s;
+  M[5] = th[3] - (th[4] * fr.cx + th[5] * fr.cy) / s;
+}
+
+// The fit of `o` on the device-resident flow f; dw (dense H x W weights) and
+// ds (dense H x W states) may be nullptr, d_inl (dense H x W) too.  Pass 0,
+// o.iters robust passes and the last pass are queued as one chain: per pass
+// the tile sums, the group tree down to <= 64 values, then the last level with
+// the solve, th and c2 staying on the device.  One small read-back and one
+// stream synchronisation at the end.
+void fit_motion_dev(of_ctx *c, const F2 &f, const float *dw, const uint8_t *ds, const of_motion_opts &o,
+                    of_motion_fit *out, float *d_inl) {
+  const int H = f.H, W = f.W;
+  const int ntx = (W + MOT_TW - 1) / MOT_TW, nty = (H + MOT_TH - 1) / MOT_TH;
+  const int nt = ntx * nty;  // < 2^31 / 8
+  const int s0 = nt, s1 = (nt + 63) / 64;
+  double *rec[2] = {(double *)c->arena.alloc(sizeof(double) * MOT_NS * s0),
+                    (double *)c->arena.alloc(sizeof(double) * MOT_NS * s1)};
+  const int stride[2] = {s0, s1};
+  MotionState *ms = (MotionState *)c->arena.alloc(sizeof(MotionState));
+  MotionFrame fr;
+  fr.s = 0.5 * (double)(H > W ? H : W);
+  fr.cx = 0.5 * (double)(W - 1);
+  fr.cy = 0.5 * (double)(H - 1);
+  const double kappa2 = o.kappa * o.kappa, cmin2 = o.c_min * o.c_min;
+  c->cur_px = (double)H * W;
+  launch(c, "motion_init", k_motion_init, dim3(1), dim3(64), 0, ms, cmin2);
+  for (int k = 0; k <= o.iters + 1; ++k) {
+    const int pass = k == 0 ? MOT_PASS_FIRST : (k <= o.iters ? MOT_PASS_ROBUST : MOT_PASS_LAST);
+    launch(c, "motion_part", k_motion_part, dim3((unsigned)((nt + MOT_WAVES - 1) / MOT_WAVES)), dim3(MOT_WAVES * 64), 0,
+           (const float2 *)f.p, H, W, f.P, dw, ds, (const MotionState *)ms, pass, fr, ntx, nt, s0, rec[0],
+           pass == MOT_PASS_LAST ? d_inl : (float *)nullptr);
+    int n = nt, src = 0;
+    while (n > 64) {  // the upper levels ping-pong between the two buffers
+      const int ng = (n + 63) / 64;
+      launch(c, "motion_group", k_motion_group, dim3((unsigned)((ng + MOT_WAVES - 1) / MOT_WAVES)),
+             dim3(MOT_WAVES * 64), 0, (const double *)rec[src], n, stride[src], rec[src ^ 1], stride[src ^ 1],
+             (const MotionState *)ms, pass);
+      n = ng;
+      src ^= 1;
+    }
+    launch(c, "motion_final", k_motion_final, dim3(1), dim3(64), 0, (const double *)rec[src], n, stride[src], ms, pass,
+           o.model, kappa2, o.decay, cmin2);
+  }
+  MotionState h;
+  HIPCHK(hipMemcpyAsync(&h, ms, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  for (int k = 0; k < 6; ++k) out->theta[k] = h.th[k];
+  motion_matrix(h.th, fr, out->matrix);
+  out->cutoff = std::sqrt(h.c2);
+  out->support = h.sums[0];
+  out->rms = std::sqrt(h.sums[12] / h.sums[0]);
+  out->passes = h.passes;
+  out->degenerate = h.degenerate;
+}
+
+// device-resident frame (dense H x W x C) through the matrix A into the host buffers
+void warp_affine_dev(of_ctx *c, const float *dim, int H, int W, int C, const double A[6], float *out, uint8_t *valid) {
+  const size_t px = (size_t)H * W;
+  float *dout = (float *)c->arena.alloc(sizeof(float) * px * C);
+  uint8_t *dv = valid ? (uint8_t *)c->arena.alloc(px) : nullptr;
+  AffineMat M;
+  for (int k = 0; k < 6; ++k) M.a[k] = A[k];
+  c->cur_px = (double)px;
+  const Grid2 g = grid2(H, W);
+  launch(c, "warp_affine", k_warp_affine, g.grid, g.block, 0, dim, C, M, H, W, dout, dv);
+  HIPCHK(hipMemcpyAsync(out, dout, sizeof(float) * px * C, hipMemcpyDeviceToHost, c->stream));
+  if (valid) HIPCHK(hipMemcpyAsync(valid, dv, px, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+}
+
+// ---- path smoothing: 2 x 3 matrices [a b tx; c d ty] on the host ----
+const Mat6 MAT6_I = {{1.0, 0.0, 0.0, 0.0, 1.0, 0.0}};
+
+bool mat6_invertible(const Mat6 &m) {
+  OF_NOCONTRACT
+  for (double v : m.a)
+    if (!std::isfinite(v)) return false;
+  const double det = m.a[0] * m.a[4] - m.a[1] * m.a[3];
+  return std::fabs(det) >= 1e-12;
+}
+// the inverse of an invertible matrix
+Mat6 mat6_inv(const Mat6 &m) {
+  OF_NOCONTRACT
+  const double a = m.a[0], b = m.a[1], tx = m.a[2], cc = m.a[3], d = m.a[4], ty = m.a[5];
+  const double det = a * d - b * cc;
+  const double ia = d / det, ib = -b / det, ic = -cc / det, id = a / det;
+  return Mat6{{ia, ib, -(ia * tx + ib * ty), ic, id, -(ic * tx + id * ty)}};
+}
+// X o Y: Y first
+Mat6 mat6_mul(const Mat6 &X, const Mat6 &Y) {
+  OF_NOCONTRACT
+  const double *x = X.a, *y = Y.a;
+  return Mat6{{x[0] * y[0] + x[1] * y[3], x[0] * y[1] + x[1] * y[4], (x[0] * y[2] + x[1] * y[5]) + x[2],
+               x[3] * y[0] + x[4] * y[3], x[3] * y[1] + x[4] * y[4], (x[3] * y[2] + x[4] * y[5]) + x[5]}};
+}
+
+// S_t of the session: the Gaussian-weighted mean of the paths from frame t to
+// its neighbours t + d, d = 0, -1, +1, -2, +2, ... within the radius and the
+// clip so far (frames 0 .. s->frames - 1; M_k links k and k + 1)
+Mat6 stab_smooth(const Stabilizer *s, int t) {
+  OF_NOCONTRACT
+  const int R = s->opt.radius;
+  const double two_s2 = (2.0 * s->opt.sigma_t) * s->opt.sigma_t;
+  auto M = [&](int k) -> const Mat6 & { return s->motion[k - s->motion0]; };
+  double num[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, den = 0.0;
+  Mat6 back = MAT6_I, fwd = MAT6_I;  // P(t -> t - d), P(t -> t + d)
+  auto add = [&](const Mat6 &P, int d) {
+    OF_NOCONTRACT
+    const double g = std::exp(-((double)d * (double)d) / two_s2);
+    for (int e = 0; e < 6; ++e) num[e] = num[e] + g * P.a[e];
+    den = den + g;
+  };
+  add(MAT6_I, 0);
+  for (int d = 1; d <= R; ++d) {
+    if (t - d >= 0) {
+      back = mat6_mul(mat6_inv(M(t - d)), back);
+      add(back, d);
+    }
+    if (t + d <= s->frames - 1) {
+      fwd = mat6_mul(M(t + d - 1), fwd);
+      add(fwd, d);
+    }
+  }
+  Mat6 S;
+  for (int e = 0; e < 6; ++e) S.a[e] = num[e] / den;
+  return S;
+}
+
+void stabilizer_free(of_ctx *c) {
+  Stabilizer *s = c->stab;
+  if (!s) return;
+  hipSetDevice(c->device);
+  if (c->stream) hipStreamSynchronize(c->stream);
+  for (float *p : s->frame)
+    if (p) hipFree(p);
+  delete s;
+  c->stab = nullptr;
+}
+
+// frame t of the session warped onto the smoothed path, into the host buffers
+void stab_emit(of_ctx *c, Stabilizer *s, int t, float *out, uint8_t *out_valid, double *out_transform,
+               int32_t *degenerate) {
+  const Mat6 S = stab_smooth(s, t);
+  if (out_transform)
+    for (int e = 0; e < 6; ++e) out_transform[e] = S.a[e];
+  Mat6 inv = MAT6_I;
+  if (mat6_invertible(S)) inv = mat6_inv(S);
+  else *degenerate |= 4;
+  warp_affine_dev(c, s->frame[t % (s->opt.radius + 1)], s->H, s->W, s->C, inv.a, out, out_valid);
+  // motions before t + 1 - radius are not needed again
+  while (s->motion0 < t + 1 - s->opt.radius && !s->motion.empty()) {
+    s->motion.pop_front();
+    ++s->motion0;
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+int of_fit_motion(of_ctx *c, const float *uv, int H, int W, const float *weight, const uint8_t *state,
+                  const of_motion_opts *o, of_motion_fit *out, float *out_inlier) {
+  API_BEGIN(c)
+  REQUIRE(uv && out, OF_EINVAL, "bad arguments");
+  check_motion_frame(H, W);
+  check_motion_opts(o);
+  const size_t px = (size_t)H * W;
+  if (weight)
+    for (size_t k = 0; k < px; ++k)
+      REQUIRE(std::isfinite(weight[k]) && weight[k] >= 0, OF_EINVAL, "weight must be finite and >= 0 everywhere");
+  const F2 f = upload_f2(c, uv, H, W);
+  float *dw = nullptr, *dinl = nullptr;
+  uint8_t *ds = nullptr;
+  if (weight) {
+    dw = (float *)c->arena.alloc(sizeof(float) * px);
+    HIPCHK(hipMemcpyAsync(dw, weight, sizeof(float) * px, hipMemcpyHostToDevice, c->stream));
+  }
+  if (state) {
+    ds = (uint8_t *)c->arena.alloc(px);
+    HIPCHK(hipMemcpyAsync(ds, state, px, hipMemcpyHostToDevice, c->stream));
+  }
+  if (out_inlier) dinl = (float *)c->arena.alloc(sizeof(float) * px);
+  fit_motion_dev(c, f, dw, ds, *o, out, dinl);
+  if (out_inlier) {
+    HIPCHK(hipMemcpyAsync(out_inlier, dinl, sizeof(float) * px, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+  }
+  API_END(c)
+}
+
+int of_warp_affine(of_ctx *c, const float *im, int H, int W, int C, const double A[6], float *out, uint8_t *valid) {
+  API_BEGIN(c)
+  REQUIRE(im && A && out, OF_EINVAL, "bad arguments");
+  REQUIRE(C >= 1 && C <= OF_MAX_NC, OF_EINVAL, "images must have 1 to 4 channels");
+  check_motion_frame(H, W);
+  const size_t px = (size_t)H * W;
+  float *dim = (float *)c->arena.alloc(sizeof(float) * px * C);
+  HIPCHK(hipMemcpyAsync(dim, im, sizeof(float) * px * C, hipMemcpyHostToDevice, c->stream));
+  warp_affine_dev(c, dim, H, W, C, A, out, valid);
+  API_END(c)
+}
+
+int of_stab_open(of_ctx *c, const of_params *P, int H, int W, int C, const of_stab_opts *o) {
+  API_BEGIN(c)
+  REQUIRE(!c->stab, OF_EINVAL, "a stabiliser is open on this context (of_stab_close first)");
+  REQUIRE(P, OF_EINVAL, "bad arguments");
+  REQUIRE(C == 1 || C == 3, OF_EINVAL, "frames must be (H,W) or (H,W,3)");
+  check_motion_frame(H, W);
+  check_stab_opts(o);
+  check_params(P);
+  Stabilizer *s = new Stabilizer();
+  c->stab = s;
+  try {
+    s->H = H;
+    s->W = W;
+    s->C = C;
+    s->P = *P;
+    s->opt = *o;
+    s->frame.assign(o->radius + 1, nullptr);
+    const size_t fb = sizeof(float) * (size_t)H * W * C;
+    for (float *&p : s->frame) {
+      HIPCHK(hipMalloc(&p, fb));
+      s->bytes += fb;
+    }
+  } catch (...) {
+    stabilizer_free(c);
+    throw;
+  }
+  API_END(c)
+}
+
+int of_stab_push(of_ctx *c, const float *frame, float *out, uint8_t *out_valid, double *out_transform,
+                 double *out_motion, int32_t *degenerate, int32_t *out_index) {
+  API_BEGIN(c)
+  Stabilizer *s = c->stab;
+  REQUIRE(s, OF_EINVAL, "no stabiliser is open on this context (of_stab_open first)");
+  REQUIRE(frame && out && degenerate && out_index, OF_EINVAL, "bad arguments");
+  REQUIRE(!s->flushed, OF_EINVAL, "the stabiliser has been flushed (of_stab_close, then open again)");
+  const int H = s->H, W = s->W, C = s->C, R = s->opt.radius, k = s->frames;
+  const size_t px = (size_t)H * W;
+  float *cur = s->frame[k % (R + 1)];
+  HIPCHK(hipMemcpyAsync(cur, frame, sizeof(float) * px * C, hipMemcpyHostToDevice, c->stream));
+  *degenerate = 0;
+  if (k > 0) {
+    of_params P = s->P;
+    F2 uf = init_flow(c, nullptr, H, W), ub = init_flow(c, nullptr, H, W);
+    uint8_t *sf = (uint8_t *)c->arena.alloc(px);
+    estimate_bidir_dev(c, &P, s->frame[(k - 1) % (R + 1)], cur, H, W, C, uf, ub, s->opt.alpha1, s->opt.alpha2, sf,
+                       nullptr, nullptr, nullptr);
+    of_motion_fit fit;
+    fit_motion_dev(c, uf, nullptr, sf, s->opt.fit, &fit, nullptr);
+    Mat6 M;
+    for (int e = 0; e < 6; ++e) M.a[e] = fit.matrix[e];
+    *degenerate = fit.degenerate;
+    if (!mat6_invertible(M)) {
+      M = MAT6_I;
+      *degenerate |= 4;
+    }
+    s->motion.push_back(M);
+    if (out_motion)
+      for (int e = 0; e < 6; ++e) out_motion[e] = M.a[e];
+  }
+  s->frames = k + 1;
+  *out_index = -1;
+  if (k >= R) {
+    stab_emit(c, s, k - R, out, out_valid, out_transform, degenerate);
+    s->next_out = k - R + 1;
+    *out_index = k - R;
+  } else {
+    HIPCHK(hipStreamSynchronize(c->stream));  // the caller's frame has been read
+  }
+  API_END(c)
+}
+
+int of_stab_flush(of_ctx *c, float *out, uint8_t *out_valid, double *out_transform, int32_t *degenerate,
+                  int32_t *out_index) {
+  API_BEGIN(c)
+  Stabilizer *s = c->stab;
+  REQUIRE(s, OF_EINVAL, "no stabiliser is open on this context (of_stab_open first)");
+  REQUIRE(out && degenerate && out_index, OF_EINVAL, "bad arguments");
+  s->flushed = true;
+  *degenerate = 0;
+  *out_index = -1;
+  if (s->next_out < s->frames) {
+    stab_emit(c, s, s->next_out, out, out_valid, out_transform, degenerate);
+    *out_index = s->next_out++;
+  }
+  API_END(c)
+}
+
+int of_stab_close(of_ctx *c) {
+  if (!c) return OF_EINVAL;
+  if (!c->stab) return fail(c, OfError{OF_EINVAL, "no stabiliser is open on this context (of_stab_open first)"});
+  stabilizer_free(c);
+  return OF_OK;
+}
+
+}  // extern "C"

@@ -145,6 +145,27 @@ class OfFuseOpts(C.Structure):
                 ("alpha1", C.c_double), ("alpha2", C.c_double)]
 
 
+# global motion and stabilisation (include/optflow.h, "Global motion estimation")
+MOTION_MODEL = {"translation": 0, "similarity": 1, "affine": 2}
+MOTION_MAX_ITERS = 64
+STAB_MAX_RADIUS = 30
+
+
+class OfMotionOpts(C.Structure):
+    _fields_ = [("model", C.c_int32), ("iters", C.c_int32), ("kappa", C.c_double), ("decay", C.c_double),
+                ("c_min", C.c_double)]
+
+
+class OfMotionFit(C.Structure):
+    _fields_ = [("theta", C.c_double * 6), ("matrix", C.c_double * 6), ("cutoff", C.c_double),
+                ("support", C.c_double), ("rms", C.c_double), ("passes", C.c_int32), ("degenerate", C.c_int32)]
+
+
+class OfStabOpts(C.Structure):
+    _fields_ = [("fit", OfMotionOpts), ("radius", C.c_int32), ("pad_", C.c_int32), ("sigma_t", C.c_double),
+                ("alpha1", C.c_double), ("alpha2", C.c_double)]
+
+
 def penalty(kind, p0=1.0, p1=0.0):
     return OfPenalty(PENALTY[kind], 0, float(p0), float(p1))
 

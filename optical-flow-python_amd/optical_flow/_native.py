@@ -11,7 +11,7 @@ import threading
 import numpy as np
 
 from optical_flow._abi import (OfParams, OfStats, OfCgGeometry, OfSolveRecord, OfProgressFn, OfTrackOpts, OfFuseOpts,
-                               OF_ABI_VERSION, OF_EINVAL, OF_ENOTSUP)
+                               OfMotionOpts, OfMotionFit, OfStabOpts, OF_ABI_VERSION, OF_EINVAL, OF_ENOTSUP)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("OPTFLOW_LIB", os.path.join(_HERE, "_lib", "liboptflow.so"))
@@ -77,6 +77,13 @@ _SIGS = {
     "of_denoise_push": ([_vp, _fp, _fp, _fp, _i32p], C.c_int),
     "of_denoise_flush": ([_vp, _fp, _fp, _i32p], C.c_int),
     "of_denoise_close": ([_vp], C.c_int),
+    "of_fit_motion": ([_vp, _fp, C.c_int, C.c_int, _fp, _u8p, C.POINTER(OfMotionOpts), C.POINTER(OfMotionFit), _fp],
+                      C.c_int),
+    "of_warp_affine": ([_vp, _fp, C.c_int, C.c_int, C.c_int, _dp, _fp, _u8p], C.c_int),
+    "of_stab_open": ([_vp, C.POINTER(OfParams), C.c_int, C.c_int, C.c_int, C.POINTER(OfStabOpts)], C.c_int),
+    "of_stab_push": ([_vp, _fp, _fp, _u8p, _dp, _dp, _i32p, _i32p], C.c_int),
+    "of_stab_flush": ([_vp, _fp, _u8p, _dp, _i32p, _i32p], C.c_int),
+    "of_stab_close": ([_vp], C.c_int),
     "of_compute_flow_base": ([_vp, C.POINTER(OfParams), _fp, C.c_int, C.c_int, C.c_int, _fp, C.c_int,
                               C.c_double, _fp, _fp], C.c_int),
     "of_alt_ba_flow_base": ([_vp, C.POINTER(OfParams), _fp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, _fp,

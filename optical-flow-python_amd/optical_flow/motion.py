@@ -1,0 +1,241 @@
+"""Global (camera) motion from a dense flow, and video stabilisation: the
+dominant motion of a flow field is fitted on the GPU as a translation, a
+similarity or an affine map by iteratively reweighted least squares with a
+decreasing Tukey cutoff; a stabiliser smooths the chain of those motions over
+a clip and warps every frame onto the smoothed camera path.
+include/optflow.h ("Global motion estimation and video stabilisation") states
+the arithmetic; in a session the frames and flows stay on the GPU
+(of_stab_*), only the six numbers of each motion visit the host.
+
+Flows are (H, W, 2) with u along columns, as everywhere in the package; masks
+are forward_backward_check's (0 consistent, anything else left out).  A motion
+is a (2, 3) matrix acting on points (column, row, 1)."""
+import ctypes as C
+from collections import namedtuple
+
+import numpy as np
+
+from optical_flow import _abi
+from optical_flow import _native as nat
+from optical_flow.methods.config import load_of_method
+from optical_flow.temporal import _flow, _number, _planar32, _state
+from optical_flow.tracking import _frame_size, _i32ptr, _int_in
+
+MotionFit = namedtuple("MotionFit", "matrix theta cutoff support rms passes degenerate inliers")
+MotionFit.__doc__ = """Result of fit_motion: `matrix` (2, 3) maps a point (column, row) of the
+flow's first frame to the second; `theta` the six parameters in normalised
+coordinates; `cutoff` the final Tukey cutoff in pixels; `support` the sum of
+the final weights; `rms` the weighted rms residual in pixels; `passes` the
+solving passes run; `degenerate` bit flags (1 a pass lost rank and solved the
+translation, 2 no support); `inliers` the (H, W) float64 final weights, or
+None."""
+
+
+def _motion_opts(model='affine', iters=10, kappa=2.0, decay=0.5, c_min=0.5):
+    """of_motion_opts from the keyword arguments; ValueError for anything the
+    library would refuse (ranges of include/optflow.h)."""
+    if not isinstance(model, str) or model not in _abi.MOTION_MODEL:
+        raise ValueError(f"model must be one of {sorted(_abi.MOTION_MODEL)}, got {model!r}")
+    decay = _number("decay", decay, True)
+    if decay > 1.0:
+        raise ValueError(f"decay must be in (0, 1], got {decay!r}")
+    return _abi.OfMotionOpts(_abi.MOTION_MODEL[model], _int_in("iters", iters, 0, _abi.MOTION_MAX_ITERS),
+                             _number("kappa", kappa, True), decay, _number("c_min", c_min, True))
+
+
+def _matrix(name, m):
+    m = np.asarray(m)
+    if m.shape != (2, 3) or m.dtype.kind not in "fiu":
+        raise ValueError(f"{name} must be a (2, 3) array of numbers, got {m.dtype} {m.shape}")
+    return np.ascontiguousarray(m, dtype=np.float64)
+
+
+def fit_motion(flow, model='affine', weight=None, state=None, iters=10, kappa=2.0, decay=0.5, c_min=0.5,
+               return_inliers=False):
+    """The dominant motion of `flow` (H, W, 2) as a MotionFit: `model` is
+    'translation', 'similarity' or 'affine'.  Pixels whose flow is not finite
+    or whose `state` (an (H, W) forward-backward mask, or None) is not 0 are
+    left out; `weight` (an (H, W) array, finite and >= 0, or None) weighs the
+    rest.  Pass 0 is plain least squares; `iters` Tukey-weighted passes follow,
+    the cutoff starting at `kappa` times the flow's rms and shrinking by
+    `decay` (on its square) per pass down to `c_min` pixels (of_fit_motion).
+    With `return_inliers` the final weights come back as `inliers`: near 1 on
+    the camera motion, 0 on what moves otherwise."""
+    flow = _flow("flow", flow)
+    H, W = flow.shape[:2]
+    _frame_size(H, W)
+    opts = _motion_opts(model, iters, kappa, decay, c_min)
+    w = nat.data_weight(weight, H, W)
+    st = _state("state", state, H, W)
+    fit = _abi.OfMotionFit()
+    inl = np.empty((H, W), dtype=np.float32) if return_inliers else None
+    ctx = nat.context()
+    ctx.check(ctx.lib.of_fit_motion(ctx.handle, nat.ptr(_planar32(flow)), H, W, nat.ptr(w), nat.u8ptr(st),
+                                    C.byref(opts), C.byref(fit), nat.ptr(inl)))
+    return MotionFit(np.array(fit.matrix, dtype=np.float64).reshape(2, 3), np.array(fit.theta, dtype=np.float64),
+                     fit.cutoff, fit.support, fit.rms, fit.passes, fit.degenerate,
+                     inl.astype(np.float64) if return_inliers else None)
+
+
+def warp_affine(im, matrix, return_valid=False):
+    """`im`, (H, W) or (H, W, C) with C <= 4, sampled bilinearly through the
+    (2, 3) `matrix`, which maps an output pixel (column, row) to its source
+    position: float64 in im's shape, 0 where the source lies outside the frame
+    or is not finite; with `return_valid` also the (H, W) uint8 mask of the
+    pixels that have a source (of_warp_affine)."""
+    im = np.asarray(im)
+    if im.ndim not in (2, 3) or im.size == 0 or im.dtype.kind not in "fiu":
+        raise ValueError(f"im must be a non-empty (H, W) or (H, W, C) array of numbers, got {im.dtype} {im.shape}")
+    Cc = 1 if im.ndim == 2 else im.shape[2]
+    if not 1 <= Cc <= _abi.FUSE_MAX_CHANNELS:
+        raise ValueError(f"im must have 1..{_abi.FUSE_MAX_CHANNELS} channels, got {Cc}")
+    H, W = im.shape[:2]
+    _frame_size(H, W)
+    A = _matrix("matrix", matrix)
+    out = np.empty(im.shape, dtype=np.float32)
+    valid = np.empty((H, W), dtype=np.uint8) if return_valid else None
+    ctx = nat.context()
+    ctx.check(ctx.lib.of_warp_affine(ctx.handle, nat.ptr(nat.f32(np.asarray(im, dtype=float))), H, W, Cc,
+                                     nat.dptr(A), nat.ptr(out), nat.u8ptr(valid)))
+    out = out.astype(np.float64)
+    return (out, valid) if return_valid else out
+
+
+class Stabilizer:
+    """Video stabiliser over frames of one shape, (H, W) or (H, W, 3): the last
+    radius + 1 frames stay on the GPU (of_stab_open / _push / _flush).
+
+        with Stabilizer(frames[0].shape) as st:
+            for f in frames:
+                r = st.push(f)          # None for the first `radius` frames,
+                ...                     # then (index, frame) of frame index
+            for index, frame in st.flush():
+                ...                     # the last `radius` frames
+
+    Every push after the first estimates estimate_flow_bidirectional(previous
+    frame, frame, method, params, alpha1, alpha2) and fits the motion between
+    the two (fit_motion on the forward flow with its mask as `state`, `model`
+    and the fit options).  Frame t comes back warped onto the camera path
+    smoothed over frames t - radius .. t + radius with a Gaussian window of
+    `sigma_t` frames, float64 in the input's shape.  After a push or a flush
+    step `last_motion` holds the (2, 3) motion fitted in that push (None for
+    the first frame and in flush), `last_transform` the (2, 3) S_t of the
+    frame returned, `last_valid` its (H, W) uint8 mask of pixels that have a
+    source and `last_degenerate` the flags (fit_motion's, | 4 where a motion
+    could not be inverted and the identity took its place).  One stabiliser per
+    context: by default the calling thread's context (other calls of the
+    package may run between pushes), or a `context` (_native.Context) of your
+    own."""
+
+    def __init__(self, shape, method='classic+nl-fast', params=None, model='similarity', radius=8, sigma_t=3.0,
+                 iters=10, kappa=2.0, decay=0.5, c_min=0.5, alpha1=0.01, alpha2=0.5, context=None):
+        self._ctx = None
+        shape = tuple(int(s) for s in shape)
+        if len(shape) not in (2, 3) or (len(shape) == 3 and shape[2] != 3):
+            raise ValueError(f"shape must be (H, W) or (H, W, 3), got {shape}")
+        H, W = shape[:2]
+        _frame_size(H, W)
+        self._opts = _abi.OfStabOpts(_motion_opts(model, iters, kappa, decay, c_min),
+                                     _int_in("radius", radius, 1, _abi.STAB_MAX_RADIUS), 0,
+                                     _number("sigma_t", sigma_t, True), _number("alpha1", alpha1, False),
+                                     _number("alpha2", alpha2, False))
+        ope = load_of_method(method)
+        if params is not None:
+            ope.parse_input_parameter(params)
+        P = ope.to_params()
+        P.guide_mode = int(ope._METHOD == 'classic_nl' and ope.color_images is not None)
+        self.shape, self.H, self.W, self.channels = shape, H, W, 3 if len(shape) == 3 else 1
+        self.radius = self._opts.radius
+        self.frames = 0
+        self.last_motion = self.last_transform = self.last_valid = None
+        self.last_degenerate = 0
+        ctx = nat.context() if context is None else context
+        ctx.check(ctx.lib.of_stab_open(ctx.handle, C.byref(P), H, W, self.channels, C.byref(self._opts)))
+        self._ctx = ctx
+
+    def _buffers(self):
+        return (np.empty(self.shape, dtype=np.float32), np.empty((self.H, self.W), dtype=np.uint8),
+                np.empty(6, dtype=np.float64), np.zeros(1, dtype=np.int32), np.full(1, -1, dtype=np.int32))
+
+    def _result(self, out, valid, S, deg, idx):
+        self.last_degenerate = int(deg[0])
+        if idx[0] < 0:
+            return None
+        self.last_transform, self.last_valid = S.reshape(2, 3).copy(), valid
+        return int(idx[0]), out.astype(np.float64)
+
+    def push(self, frame):
+        """The next frame.  Returns (index, frame) of the stabilised frame that
+        became complete, float64 in the input's shape, or None while fewer
+        than radius + 1 frames have been pushed."""
+        if self._ctx is None:
+            raise ValueError("the stabiliser is closed")
+        f = np.asarray(frame)
+        if f.shape != self.shape or f.dtype.kind not in "fiu":
+            raise ValueError(f"frames must be {self.shape} arrays of numbers, got {f.dtype} {f.shape}")
+        f = nat.f32(np.asarray(f, dtype=float))
+        out, valid, S, deg, idx = self._buffers()
+        M = np.empty(6, dtype=np.float64)
+        ctx = self._ctx
+        ctx.check(ctx.lib.of_stab_push(ctx.handle, nat.ptr(f), nat.ptr(out), nat.u8ptr(valid), nat.dptr(S),
+                                       nat.dptr(M), _i32ptr(deg), _i32ptr(idx)))
+        self.last_motion = M.reshape(2, 3) if self.frames > 0 else None
+        self.frames += 1
+        return self._result(out, valid, S, deg, idx)
+
+    def flush(self):
+        """Yields (index, frame) for the frames still pending at the end of
+        the clip, smoothed over the neighbours that exist.  No push after it."""
+        if self._ctx is None:
+            raise ValueError("the stabiliser is closed")
+        ctx = self._ctx
+        while True:
+            out, valid, S, deg, idx = self._buffers()
+            ctx.check(ctx.lib.of_stab_flush(ctx.handle, nat.ptr(out), nat.u8ptr(valid), nat.dptr(S), _i32ptr(deg),
+                                            _i32ptr(idx)))
+            self.last_motion = None
+            r = self._result(out, valid, S, deg, idx)
+            if r is None:
+                return
+            yield r
+
+    def close(self):
+        if self._ctx is not None:
+            ctx, self._ctx = self._ctx, None
+            if ctx.handle:
+                ctx.check(ctx.lib.of_stab_close(ctx.handle))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def stabilize_frames(frames, method='classic+nl-fast', model='similarity', radius=8, sigma_t=3.0, params=None,
+                     iters=10, kappa=2.0, decay=0.5, c_min=0.5, alpha1=0.01, alpha2=0.5, return_transforms=False):
+    """Stabilise `frames` (a sequence of at least one (H, W) or (H, W, 3)
+    frame of one shape) with a Stabilizer: returns (T, H, W[, 3]) float64; with
+    `return_transforms` also the (T, 2, 3) float64 S_t each frame was moved
+    by (a point of frame t lies at S_t^-1 of it in the output)."""
+    frames = [np.asarray(f) for f in frames]
+    if not frames or any(f.shape != frames[0].shape for f in frames):
+        raise ValueError("frames must be a non-empty sequence of frames of one shape")
+    out = np.empty((len(frames),) + frames[0].shape, dtype=np.float64)
+    tr = np.empty((len(frames), 2, 3), dtype=np.float64)
+    with Stabilizer(frames[0].shape, method, params, model, radius, sigma_t, iters, kappa, decay, c_min, alpha1,
+                    alpha2) as st:
+        def take(r):
+            if r is not None:
+                out[r[0]], tr[r[0]] = r[1], st.last_transform
+        for f in frames:
+            take(st.push(f))
+        for r in st.flush():
+            take(r)
+    return (out, tr) if return_transforms else out
