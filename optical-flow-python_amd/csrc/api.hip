@@ -68,9 +68,7 @@ int of_ctx_create(int device, of_ctx **out) {
 int of_ctx_destroy(of_ctx *c) {
   if (!c) return OF_OK;
   if (c->pool) of_pairs_close(c);
-  tracker_free(c);
-  denoiser_free(c);
-  stabilizer_free(c);
+  for (int k = 0; k < SES_KINDS; ++k) session_free(c, k);
   for (of_ctx *l : c->lanes) of_ctx_destroy(l);
   c->lanes.clear();
   hipSetDevice(c->device);
@@ -171,15 +169,14 @@ int of_get_option(of_ctx *c, int option, int64_t *value) {
     case OF_OPT_DEVICE_BYTES: {
       // grow-only device buffers of the context and its lanes: the arena
       // chunks, the pipelined SOR's sweep ring and the RCCL gather buffer;
-      // and an open point tracker's, temporal denoiser's and stabiliser's buffers
+      // and the open sessions' (point tracker, temporal denoiser, stabiliser) buffers
       auto held = [](const of_ctx *x) {
         return (int64_t)(x->arena.reserved() + x->sor_ring_cap + x->gather_cap);
       };
       int64_t n = held(c);
       for (of_ctx *l : c->lanes) n += held(l);
-      if (c->trk) n += (int64_t)c->trk->bytes;
-      if (c->den) n += (int64_t)c->den->bytes;
-      if (c->stab) n += (int64_t)c->stab->bytes;
+      for (const Session *s : c->session)
+        if (s) n += (int64_t)s->bytes;
       *value = n;
       return OF_OK;
     }
@@ -355,15 +352,14 @@ int of_fb_consistency(of_ctx *c, const float *fw, const float *bw, int H, int W,
                       uint8_t *state, float *err) {
   API_BEGIN(c)
   REQUIRE(fw && bw && state && H > 0 && W > 0, OF_EINVAL, "bad arguments");
-  REQUIRE(std::isfinite(alpha1) && std::isfinite(alpha2) && alpha1 >= 0 && alpha2 >= 0, OF_EINVAL,
-          "alpha1 and alpha2 must be finite and >= 0");
+  check_alphas(alpha1, alpha2);
   const size_t n = (size_t)H * W;
   F2 f = upload_f2(c, fw, H, W), b = upload_f2(c, bw, H, W);
-  uint8_t *ds = (uint8_t *)c->arena.alloc(n);
-  float *de = err ? (float *)c->arena.alloc(sizeof(float) * n) : nullptr;
+  uint8_t *ds = new_dense<uint8_t>(c, n);
+  float *de = new_dense<float>(c, n, err);
   fb_check(c, f, b, alpha1, alpha2, ds, de, nullptr, nullptr);
-  HIPCHK(hipMemcpyAsync(state, ds, n, hipMemcpyDeviceToHost, c->stream));
-  if (err) HIPCHK(hipMemcpyAsync(err, de, sizeof(float) * n, hipMemcpyDeviceToHost, c->stream));
+  download_dense(c, state, ds, n);
+  download_dense(c, err, de, n);
   HIPCHK(hipStreamSynchronize(c->stream));
   API_END(c)
 }
@@ -373,8 +369,7 @@ int of_estimate_flow_bidir(of_ctx *c, of_params *P, const float *im1, const floa
                            double alpha2, uint8_t *state_fw, uint8_t *state_bw, of_stats *sf, of_stats *sb) {
   API_BEGIN(c)
   REQUIRE(P && im1 && im2 && out_fw && out_bw && H > 0 && W > 0, OF_EINVAL, "bad arguments");
-  REQUIRE(std::isfinite(alpha1) && std::isfinite(alpha2) && alpha1 >= 0 && alpha2 >= 0, OF_EINVAL,
-          "alpha1 and alpha2 must be finite and >= 0");
+  check_alphas(alpha1, alpha2);
   if (sf) memset(sf, 0, sizeof(*sf));
   if (sb) memset(sb, 0, sizeof(*sb));
   const WallClock wall;  // the forward pass's total_ms; the backward pass has its own
@@ -382,13 +377,12 @@ int of_estimate_flow_bidir(of_ctx *c, of_params *P, const float *im1, const floa
   float *d1, *d2;
   upload_frames(c, im1, im2, px * C, &d1, &d2);
   F2 uf = init_flow(c, init_fw, H, W), ub = init_flow(c, init_bw, H, W);
-  uint8_t *dsf = state_fw ? (uint8_t *)c->arena.alloc(px) : nullptr;
-  uint8_t *dsb = state_bw ? (uint8_t *)c->arena.alloc(px) : nullptr;
+  uint8_t *dsf = new_dense<uint8_t>(c, px, state_fw), *dsb = new_dense<uint8_t>(c, px, state_bw);
   estimate_bidir_dev(c, P, d1, d2, H, W, C, uf, ub, alpha1, alpha2, dsf, dsb, sf, sb);
   download_f2(c, uf, out_fw);
   download_f2(c, ub, out_bw);
-  if (state_fw) HIPCHK(hipMemcpyAsync(state_fw, dsf, px, hipMemcpyDeviceToHost, c->stream));
-  if (state_bw) HIPCHK(hipMemcpyAsync(state_bw, dsb, px, hipMemcpyDeviceToHost, c->stream));
+  download_dense(c, state_fw, dsf, px);
+  download_dense(c, state_bw, dsb, px);
   HIPCHK(hipStreamSynchronize(c->stream));
   if (sf) sf->total_ms = wall.ms();
   API_END(c)
@@ -399,17 +393,16 @@ int of_warp_image(of_ctx *c, const float *im, int H, int W, int C, const float *
   REQUIRE(im && uv && out && H > 0 && W > 0, OF_EINVAL, "bad arguments");
   REQUIRE(C >= 1 && C <= OF_MAX_NC, OF_EINVAL, "images must have 1 to 4 channels");
   const size_t px = (size_t)H * W;
-  float *dim = (float *)c->arena.alloc(sizeof(float) * px * C);
-  HIPCHK(hipMemcpyAsync(dim, im, sizeof(float) * px * C, hipMemcpyHostToDevice, c->stream));
+  float *dim = upload_dense(c, im, px * C);
   F2 f = upload_f2(c, uv, H, W);
-  float *dout = (float *)c->arena.alloc(sizeof(float) * px * C);
-  uint8_t *dv = valid ? (uint8_t *)c->arena.alloc(px) : nullptr;
+  float *dout = new_dense<float>(c, px * C);
+  uint8_t *dv = new_dense<uint8_t>(c, px, valid);
   c->cur_px = (double)px;
   Grid2 g = grid2(H, W);
   launch(c, "warp_image", k_warp_image, g.grid, g.block, 0, (const float *)dim, C, (const float2 *)f.p, H, W, f.P,
          dout, dv);
-  HIPCHK(hipMemcpyAsync(out, dout, sizeof(float) * px * C, hipMemcpyDeviceToHost, c->stream));
-  if (valid) HIPCHK(hipMemcpyAsync(valid, dv, px, hipMemcpyDeviceToHost, c->stream));
+  download_dense(c, out, dout, px * C);
+  download_dense(c, valid, dv, px);
   HIPCHK(hipStreamSynchronize(c->stream));
   API_END(c)
 }

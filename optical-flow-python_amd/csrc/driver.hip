@@ -13,10 +13,11 @@
 //
 // Host parts, one concern each, in dependency order (a part uses only the
 // parts above it, so none needs a forward declaration of a later one):
-//   host_core.h     errors, arena, context, profiling, launch(), API_* macros
+//   host_core.h     errors, arena, context, session base, profiling, launch(), shared checks, API_* macros
 //   host_image.hip  image / flow-field helpers, taps, pyramids, ROF, derivatives, medians
 //   host_solve.hip  CG and SOR dispatch, solve log, deferred statistics, gen_* solvers
 //   host_flow.hip   assembly dispatch, token, per-level IRLS loops, schedule, estimate_*
+//   host_session.hip what the frame-sequence sessions share: lookup and free, open and push prologues, delayed emission
 //   host_track.hip  point tracker: advance and seed steps, stage entries, the session
 //   host_fuse.hip   temporal denoising: flow composition, frame fusion, stage entries, the session
 //   host_motion.hip global motion: the robust parametric fit, the affine warp, path smoothing, the stabiliser session
@@ -52,6 +53,7 @@
 #include "host_image.hip"
 #include "host_solve.hip"
 #include "host_flow.hip"
+#include "host_session.hip"
 #include "host_track.hip"
 #include "host_fuse.hip"
 #include "host_motion.hip"

@@ -163,56 +163,64 @@ struct PairPool {
   OfError err{OF_OK, ""};
 };
 
-// the point tracker of a context (of_tracks_open, host_track.hip): its own
-// device allocations, which outlive the arena's per-call reset
-struct Tracker {
+// What the frame-sequence sessions of a context share (host_session.hip): the
+// frame size, the parameters, a ring of the last frames, the delayed-emission
+// state and the device allocations, which are the session's own and outlive
+// the arena's per-call reset.  A context holds at most one of each kind.
+enum { SES_TRACK, SES_DENOISE, SES_STAB, SES_KINDS };
+struct Session {
   int H = 0, W = 0, C = 0;
   of_params P;        // as given at open; every push starts from a copy
+  int frames = 0;     // frames pushed
+  int next_out = 0;   // the next frame to emit (delayed emitters)
+  bool flushed = false;
+  std::vector<float *> frame;  // frame k at k % frame.size(): H x W x C dense
+  std::vector<void *> owned;   // every device allocation of the session
+  size_t bytes = 0;            // of all of them
+  virtual ~Session() = default;
+  template <typename T>
+  T *alloc(size_t count) {
+    T *p = nullptr;
+    HIPCHK(hipMalloc(&p, sizeof(T) * count));
+    owned.push_back(p);
+    bytes += sizeof(T) * count;
+    return p;
+  }
+  void alloc_frames(int n) {
+    for (int k = 0; k < n; ++k) frame.push_back(alloc<float>((size_t)H * W * C));
+  }
+};
+
+// the point tracker (of_tracks_open, host_track.hip): a ring of 2 frames
+struct Tracker : Session {
   of_track_opts opt;
   int n = 0;                     // tracks in the table
-  int frames = 0;                // frames pushed
-  float *frame[2] = {nullptr, nullptr};  // H x W x C dense; frame[frames & 1] receives the next one
-  float2 *xy = nullptr;                  // the table: max_tracks entries each
+  float2 *xy = nullptr;          // the table: max_tracks entries each
   uint8_t *status = nullptr;
   int32_t *start = nullptr;
   uint8_t *occ = nullptr, *flags = nullptr;  // per cell
   int *bcnt = nullptr;                       // the cell kernels' block counts, then the total
-  size_t bytes = 0;                          // of all of the above
 };
 
-// the temporal denoiser of a context (of_denoise_open, host_fuse.hip): rings
-// of the last 2R+1 frames and of the last 2R adjacent pairs' flows and
-// forward-backward states, its own device allocations like the tracker's
-struct Denoiser {
-  int H = 0, W = 0, C = 0, pitch = 0;
-  of_params P;        // as given at open; every push starts from a copy
+// the temporal denoiser (of_denoise_open, host_fuse.hip): a ring of 2R+1
+// frames and rings of the last 2R adjacent pairs' flows and forward-backward
+// states
+struct Denoiser : Session {
+  int pitch = 0;
   of_fuse_opts opt;
-  int frames = 0;     // frames pushed
-  int next_out = 0;   // the next frame to emit
-  bool flushed = false;
-  float *frame[5] = {};                    // frame k at k % (2R+1): H x W x C dense
   float2 *fw[4] = {}, *bw[4] = {};         // pair (j, j+1) at j % 2R: pitched flows j -> j+1 and j+1 -> j
   uint8_t *sf[4] = {}, *sb[4] = {};        // their forward-backward states, H x W dense
-  size_t bytes = 0;                        // of all of the above
 };
 
-// the stabiliser of a context (of_stab_open, host_motion.hip): a ring of the
-// last R+1 frames, its own device allocations like the tracker's; the motions
-// between adjacent frames live on the host
+// the stabiliser (of_stab_open, host_motion.hip): a ring of R+1 frames; the
+// motions between adjacent frames live on the host
 struct Mat6 {
   double a[6];
 };
-struct Stabilizer {
-  int H = 0, W = 0, C = 0;
-  of_params P;        // as given at open; every push starts from a copy
+struct Stabilizer : Session {
   of_stab_opts opt;
-  int frames = 0;     // frames pushed
-  int next_out = 0;   // the next frame to emit
-  bool flushed = false;
-  std::vector<float *> frame;  // frame k at k % (R+1): H x W x C dense
   std::deque<Mat6> motion;     // M_k at k - motion0, as kept (the identity where the fit's could not be inverted)
   int motion0 = 0;
-  size_t bytes = 0;            // of the frames
 };
 
 }  // namespace
@@ -350,9 +358,7 @@ struct of_ctx {
   std::vector<Slot> slots;
   HostStage *hs = nullptr;      // of_pairs_run_host staging (lazily created)
   PairPool *pool = nullptr;     // of_pairs_open streaming batch (lanes of its own)
-  Tracker *trk = nullptr;       // of_tracks_open point tracker
-  Denoiser *den = nullptr;      // of_denoise_open temporal denoiser
-  Stabilizer *stab = nullptr;   // of_stab_open stabiliser
+  Session *session[SES_KINDS] = {};  // of_tracks_open, of_denoise_open, of_stab_open: one of each
   std::vector<of_ctx *> lanes;  // of_pairs_run pipelines: own stream, arena and solver state
   Token big_own;                // (parent) the big-phase token its lanes share
   Token *big = nullptr;         // (lane) token held through phases of >= big_px pixels
@@ -433,6 +439,18 @@ int fail(of_ctx *c, const OfError &e) {
 }
 
 thread_local std::string g_err;
+
+// ---- argument checks several parts share ----
+// the forward-backward thresholds
+void check_alphas(double alpha1, double alpha2) {
+  REQUIRE(std::isfinite(alpha1) && std::isfinite(alpha2) && alpha1 >= 0 && alpha2 >= 0, OF_EINVAL,
+          "alpha1 and alpha2 must be finite and >= 0");
+}
+// a frame size whose pixel index fits 31 bits; `what` names who needs that
+void check_frame(int H, int W, const char *what) {
+  REQUIRE(H > 0 && W > 0, OF_EINVAL, "bad arguments");
+  REQUIRE((size_t)H * W < ((size_t)1 << 31), OF_ENOTSUP, std::string(what) + " takes H * W < 2^31");
+}
 
 }  // namespace
 

@@ -776,8 +776,7 @@ void interp_frames_dev(of_ctx *c, const float *d1, const float *d2, int H, int W
 void check_interp_args(int H, int W, double alpha1, double alpha2, int n, const double *t) {
   REQUIRE((size_t)H * W < ((size_t)1 << 31), OF_ENOTSUP,
           "frame interpolation takes H * W < 2^31 (the splat key holds a 31-bit source index)");
-  REQUIRE(std::isfinite(alpha1) && std::isfinite(alpha2) && alpha1 >= 0 && alpha2 >= 0, OF_EINVAL,
-          "alpha1 and alpha2 must be finite and >= 0");
+  check_alphas(alpha1, alpha2);
   REQUIRE(n >= 1 && t, OF_EINVAL, "at least one time t");
   for (int k = 0; k < n; ++k) REQUIRE(t[k] > 0.0 && t[k] < 1.0, OF_EINVAL, "every t must lie strictly inside (0, 1)");
 }

@@ -10,12 +10,7 @@ void check_fuse_opts(const of_fuse_opts *o) {
   REQUIRE(o->patch >= 0 && o->patch <= FUSE_MAX_R, OF_EINVAL, "fuse patch must be 0..3");
   REQUIRE(std::isfinite(o->sigma) && o->sigma > 0 && std::isfinite(o->strength) && o->strength > 0, OF_EINVAL,
           "sigma and strength must be finite and > 0");
-  REQUIRE(std::isfinite(o->alpha1) && std::isfinite(o->alpha2) && o->alpha1 >= 0 && o->alpha2 >= 0, OF_EINVAL,
-          "alpha1 and alpha2 must be finite and >= 0");
-}
-void check_fuse_frame(int H, int W) {
-  REQUIRE(H > 0 && W > 0, OF_EINVAL, "bad arguments");
-  REQUIRE((size_t)H * W < ((size_t)1 << 31), OF_ENOTSUP, "temporal fusion takes H * W < 2^31");
+  check_alphas(o->alpha1, o->alpha2);
 }
 
 // out = f followed by g, device-resident; sf / sg / so: dense H x W bytes or nullptr
@@ -49,31 +44,11 @@ void fuse_dev(of_ctx *c, const float *center, int H, int W, int C, int P, int n,
          o.patch, two_s2, h2, gx, out, out_w);
 }
 
-void denoiser_free(of_ctx *c) {
-  Denoiser *d = c->den;
-  if (!d) return;
-  hipSetDevice(c->device);
-  if (c->stream) hipStreamSynchronize(c->stream);
-  for (float *p : d->frame)
-    if (p) hipFree(p);
-  for (int k = 0; k < 4; ++k)
-    for (void *p : {(void *)d->fw[k], (void *)d->bw[k], (void *)d->sf[k], (void *)d->sb[k]})
-      if (p) hipFree(p);
-  delete d;
-  c->den = nullptr;
-}
-
-template <typename T>
-void denoiser_alloc(Denoiser *d, T **p, size_t count) {
-  HIPCHK(hipMalloc(p, sizeof(T) * count));
-  d->bytes += sizeof(T) * count;
-}
-
 // Frame t of the session fused with the neighbours at offsets -1, +1, -2, +2
 // that exist among the frames pushed so far (|offset| <= radius), written to
 // the host buffers.  Offsets of 2 chain two adjacent pairs' flows.
 void denoise_emit(of_ctx *c, Denoiser *d, int t, float *out, float *out_weight) {
-  const int H = d->H, W = d->W, C = d->C, R = d->opt.radius, NF = 2 * R + 1, NP = 2 * R;
+  const int H = d->H, W = d->W, C = d->C, R = d->opt.radius, NF = (int)d->frame.size(), NP = 2 * R;
   const size_t px = (size_t)H * W;
   const float *neigh[4];
   const float2 *flow[4];
@@ -102,7 +77,7 @@ void denoise_emit(of_ctx *c, Denoiser *d, int t, float *out, float *out_weight) 
       } else {
         const int p1 = (sgn > 0 ? t + 1 : t - 2) % NP;
         const F2 comp = new_f2(c, H, W);
-        uint8_t *cs = (uint8_t *)c->arena.alloc(px);
+        uint8_t *cs = new_dense<uint8_t>(c, px);
         flow_compose_dev(c, f2(fl[p0]), f2(fl[p1]), st[p0], st[p1], comp, cs);
         flow[n] = comp.p;
         state[n] = cs;
@@ -111,16 +86,15 @@ void denoise_emit(of_ctx *c, Denoiser *d, int t, float *out, float *out_weight) 
     }
   const float *center = d->frame[t % NF];
   if (n == 0) {  // a clip of one frame
-    HIPCHK(hipMemcpyAsync(out, center, sizeof(float) * px * C, hipMemcpyDeviceToHost, c->stream));
+    download_dense(c, out, center, px * C);
     HIPCHK(hipStreamSynchronize(c->stream));
     if (out_weight) std::fill(out_weight, out_weight + px, 1.0f);
     return;
   }
-  float *dout = (float *)c->arena.alloc(sizeof(float) * px * C);
-  float *dw = out_weight ? (float *)c->arena.alloc(sizeof(float) * px) : nullptr;
+  float *dout = new_dense<float>(c, px * C), *dw = new_dense<float>(c, px, out_weight);
   fuse_dev(c, center, H, W, C, d->pitch, n, neigh, flow, state, d->opt, dout, dw);
-  HIPCHK(hipMemcpyAsync(out, dout, sizeof(float) * px * C, hipMemcpyDeviceToHost, c->stream));
-  if (out_weight) HIPCHK(hipMemcpyAsync(out_weight, dw, sizeof(float) * px, hipMemcpyDeviceToHost, c->stream));
+  download_dense(c, out, dout, px * C);
+  download_dense(c, out_weight, dw, px);
   HIPCHK(hipStreamSynchronize(c->stream));
 }
 
@@ -132,24 +106,16 @@ int of_flow_compose(of_ctx *c, const float *f, const float *g, int H, int W, con
                     const uint8_t *state_g, float *out, uint8_t *out_state) {
   API_BEGIN(c)
   REQUIRE(f && g && out, OF_EINVAL, "bad arguments");
-  check_fuse_frame(H, W);
+  check_frame(H, W, "temporal fusion");
   const size_t px = (size_t)H * W;
   const F2 df = upload_f2(c, f, H, W), dg = upload_f2(c, g, H, W), dout = new_f2(c, H, W);
-  uint8_t *dsf = nullptr, *dsg = nullptr, *dso = nullptr;
-  if (out_state) {
-    if (state_f) {
-      dsf = (uint8_t *)c->arena.alloc(px);
-      HIPCHK(hipMemcpyAsync(dsf, state_f, px, hipMemcpyHostToDevice, c->stream));
-    }
-    if (state_g) {
-      dsg = (uint8_t *)c->arena.alloc(px);
-      HIPCHK(hipMemcpyAsync(dsg, state_g, px, hipMemcpyHostToDevice, c->stream));
-    }
-    dso = (uint8_t *)c->arena.alloc(px);
-  }
+  // the states matter only where the composed state is asked for
+  uint8_t *dsf = upload_dense(c, out_state ? state_f : nullptr, px);
+  uint8_t *dsg = upload_dense(c, out_state ? state_g : nullptr, px);
+  uint8_t *dso = new_dense<uint8_t>(c, px, out_state);
   flow_compose_dev(c, df, dg, dsf, dsg, dout, dso);
   download_f2(c, dout, out);
-  if (out_state) HIPCHK(hipMemcpyAsync(out_state, dso, px, hipMemcpyDeviceToHost, c->stream));
+  download_dense(c, out_state, dso, px);
   HIPCHK(hipStreamSynchronize(c->stream));
   API_END(c)
 }
@@ -160,18 +126,11 @@ int of_fuse_frames(of_ctx *c, const float *center, int H, int W, int C, int n, c
   REQUIRE(center && neigh && flows && out, OF_EINVAL, "bad arguments");
   REQUIRE(C >= 1 && C <= FUSE_MAX_C, OF_EINVAL, "frames must have 1..4 channels");
   REQUIRE(n >= 1 && n <= FUSE_MAX_N, OF_EINVAL, "1..8 neighbours");
-  check_fuse_frame(H, W);
+  check_frame(H, W, "temporal fusion");
   check_fuse_opts(o);
   const size_t px = (size_t)H * W;
-  float *dc = (float *)c->arena.alloc(sizeof(float) * px * C);
-  float *dn = (float *)c->arena.alloc(sizeof(float) * px * C * n);
-  HIPCHK(hipMemcpyAsync(dc, center, sizeof(float) * px * C, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(dn, neigh, sizeof(float) * px * C * n, hipMemcpyHostToDevice, c->stream));
-  uint8_t *ds = nullptr;
-  if (states) {
-    ds = (uint8_t *)c->arena.alloc(px * n);
-    HIPCHK(hipMemcpyAsync(ds, states, px * n, hipMemcpyHostToDevice, c->stream));
-  }
+  float *dc = upload_dense(c, center, px * C), *dn = upload_dense(c, neigh, px * C * n);
+  uint8_t *ds = upload_dense(c, states, px * n);
   const float *pn[FUSE_MAX_N];
   const float2 *pf[FUSE_MAX_N];
   const uint8_t *pst[FUSE_MAX_N];
@@ -181,73 +140,47 @@ int of_fuse_frames(of_ctx *c, const float *center, int H, int W, int C, int n, c
     pf[k] = fk.p;
     pst[k] = ds ? ds + (size_t)k * px : nullptr;
   }
-  float *dout = (float *)c->arena.alloc(sizeof(float) * px * C);
-  float *dw = out_weight ? (float *)c->arena.alloc(sizeof(float) * px) : nullptr;
+  float *dout = new_dense<float>(c, px * C), *dw = new_dense<float>(c, px, out_weight);
   fuse_dev(c, dc, H, W, C, of_pitch(W), n, pn, pf, pst, *o, dout, dw);
-  HIPCHK(hipMemcpyAsync(out, dout, sizeof(float) * px * C, hipMemcpyDeviceToHost, c->stream));
-  if (out_weight) HIPCHK(hipMemcpyAsync(out_weight, dw, sizeof(float) * px, hipMemcpyDeviceToHost, c->stream));
+  download_dense(c, out, dout, px * C);
+  download_dense(c, out_weight, dw, px);
   HIPCHK(hipStreamSynchronize(c->stream));
   API_END(c)
 }
 
 int of_denoise_open(of_ctx *c, const of_params *P, int H, int W, int C, const of_fuse_opts *o) {
   API_BEGIN(c)
-  REQUIRE(!c->den, OF_EINVAL, "a temporal denoiser is open on this context (of_denoise_close first)");
-  REQUIRE(P, OF_EINVAL, "bad arguments");
-  REQUIRE(C == 1 || C == 3, OF_EINVAL, "frames must be (H,W) or (H,W,3)");
-  check_fuse_frame(H, W);
-  check_fuse_opts(o);
-  check_params(P);
-  Denoiser *d = new Denoiser();
-  c->den = d;
-  try {
-    d->H = H;
-    d->W = W;
-    d->C = C;
+  session_open<Denoiser>(c, SES_DENOISE, P, H, W, C, o, check_fuse_opts, [&](Denoiser *d) {
     d->pitch = of_pitch(W);
-    d->P = *P;
-    d->opt = *o;
     const size_t px = (size_t)H * W, fpx = (size_t)H * d->pitch;
-    for (int k = 0; k < 2 * o->radius + 1; ++k) denoiser_alloc(d, &d->frame[k], px * C);
+    d->alloc_frames(2 * o->radius + 1);
     for (int k = 0; k < 2 * o->radius; ++k) {
-      denoiser_alloc(d, &d->fw[k], fpx);
-      denoiser_alloc(d, &d->bw[k], fpx);
-      denoiser_alloc(d, &d->sf[k], px);
-      denoiser_alloc(d, &d->sb[k], px);
+      d->fw[k] = d->alloc<float2>(fpx);
+      d->bw[k] = d->alloc<float2>(fpx);
+      d->sf[k] = d->alloc<uint8_t>(px);
+      d->sb[k] = d->alloc<uint8_t>(px);
     }
-  } catch (...) {
-    denoiser_free(c);
-    throw;
-  }
+  });
   API_END(c)
 }
 
 int of_denoise_push(of_ctx *c, const float *frame, float *out, float *out_weight, int32_t *out_index) {
   API_BEGIN(c)
-  Denoiser *d = c->den;
-  REQUIRE(d, OF_EINVAL, "no temporal denoiser is open on this context (of_denoise_open first)");
+  Denoiser *d = session_get<Denoiser>(c, SES_DENOISE);
   REQUIRE(frame && out && out_index, OF_EINVAL, "bad arguments");
-  REQUIRE(!d->flushed, OF_EINVAL, "the temporal denoiser has been flushed (of_denoise_close, then open again)");
-  const int H = d->H, W = d->W, C = d->C, R = d->opt.radius, k = d->frames;
-  const size_t px = (size_t)H * W;
-  float *cur = d->frame[k % (2 * R + 1)];
-  HIPCHK(hipMemcpyAsync(cur, frame, sizeof(float) * px * C, hipMemcpyHostToDevice, c->stream));
+  session_not_flushed(d, SES_DENOISE);
+  const int R = d->opt.radius, k = d->frames, p = k > 0 ? (k - 1) % (2 * R) : 0;
+  const PushPair pr = session_push(c, d, frame, d->opt.alpha1, d->opt.alpha2, d->sf[p], d->sb[p], nullptr, nullptr);
   if (k > 0) {
-    const int p = (k - 1) % (2 * R);
-    of_params P = d->P;
-    F2 uf = init_flow(c, nullptr, H, W), ub = init_flow(c, nullptr, H, W);
-    estimate_bidir_dev(c, &P, d->frame[(k - 1) % (2 * R + 1)], cur, H, W, C, uf, ub, d->opt.alpha1, d->opt.alpha2,
-                       d->sf[p], d->sb[p], nullptr, nullptr);
-    const size_t fb = sizeof(float2) * (size_t)H * uf.P;  // new_f2's pitch is of_pitch(W), the ring's
-    HIPCHK(hipMemcpyAsync(d->fw[p], uf.p, fb, hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(d->bw[p], ub.p, fb, hipMemcpyDeviceToDevice, c->stream));
+    const size_t fb = sizeof(float2) * (size_t)d->H * pr.fw.P;  // new_f2's pitch is of_pitch(W), the ring's
+    HIPCHK(hipMemcpyAsync(d->fw[p], pr.fw.p, fb, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(d->bw[p], pr.bw.p, fb, hipMemcpyDeviceToDevice, c->stream));
   }
-  d->frames = k + 1;
   *out_index = -1;
-  if (k >= R) {
-    denoise_emit(c, d, k - R, out, out_weight);
-    d->next_out = k - R + 1;
-    *out_index = k - R;
+  const int t = session_next_emit(d, R, false);
+  if (t >= 0) {
+    denoise_emit(c, d, t, out, out_weight);
+    *out_index = t;
   } else {
     HIPCHK(hipStreamSynchronize(c->stream));  // the caller's frame has been read
   }
@@ -256,24 +189,17 @@ int of_denoise_push(of_ctx *c, const float *frame, float *out, float *out_weight
 
 int of_denoise_flush(of_ctx *c, float *out, float *out_weight, int32_t *out_index) {
   API_BEGIN(c)
-  Denoiser *d = c->den;
-  REQUIRE(d, OF_EINVAL, "no temporal denoiser is open on this context (of_denoise_open first)");
+  Denoiser *d = session_get<Denoiser>(c, SES_DENOISE);
   REQUIRE(out && out_index, OF_EINVAL, "bad arguments");
-  d->flushed = true;
   *out_index = -1;
-  if (d->next_out < d->frames) {
-    denoise_emit(c, d, d->next_out, out, out_weight);
-    *out_index = d->next_out++;
+  const int t = session_next_emit(d, d->opt.radius, true);
+  if (t >= 0) {
+    denoise_emit(c, d, t, out, out_weight);
+    *out_index = t;
   }
   API_END(c)
 }
 
-int of_denoise_close(of_ctx *c) {
-  if (!c) return OF_EINVAL;
-  if (!c->den)
-    return fail(c, OfError{OF_EINVAL, "no temporal denoiser is open on this context (of_denoise_open first)"});
-  denoiser_free(c);
-  return OF_OK;
-}
+int of_denoise_close(of_ctx *c) { return session_close(c, SES_DENOISE); }
 
 }  // extern "C"

@@ -45,6 +45,25 @@ Img upload_new_img(of_ctx *c, const float *host, int H, int W, int C) {
 void copy_img(of_ctx *c, const Img &dst, const Img &src) {
   HIPCHK(hipMemcpyAsync(dst.p, src.p, sizeof(float) * src.ps() * src.C, hipMemcpyDeviceToDevice, c->stream));
 }
+// ---- dense data: n values, no pitch ----
+// an arena buffer where `want` says so (an optional output's device side), else nullptr
+template <typename T>
+T *new_dense(of_ctx *c, size_t n, bool want = true) {
+  return want ? (T *)c->arena.alloc(sizeof(T) * n) : nullptr;
+}
+// the host data's arena copy, on the context's stream; nullptr for nullptr
+template <typename T>
+T *upload_dense(of_ctx *c, const T *host, size_t n) {
+  T *d = new_dense<T>(c, n, host != nullptr);
+  if (host) HIPCHK(hipMemcpyAsync(d, host, sizeof(T) * n, hipMemcpyHostToDevice, c->stream));
+  return d;
+}
+// device -> host where the caller gave a host buffer
+template <typename T, typename D>
+void download_dense(of_ctx *c, T *host, const D *dev, size_t n) {
+  static_assert(std::is_same<T, D>::value, "host and device buffers of one type");
+  if (host) HIPCHK(hipMemcpyAsync(host, dev, sizeof(T) * n, hipMemcpyDeviceToHost, c->stream));
+}
 // planar host/dense-device uv <-> pitched float2
 void f2_from_dense(of_ctx *c, const F2 &f, const float *dense_dev) {
   Grid2 g = grid2(f.H, f.W);
@@ -58,15 +77,13 @@ void f2_to_dense(of_ctx *c, const F2 &f, float *dense_dev) {
 }
 F2 upload_f2(of_ctx *c, const float *host, int H, int W) {
   F2 f = new_f2(c, H, W);
-  float *d = (float *)c->arena.alloc(sizeof(float) * 2 * (size_t)H * W);
-  HIPCHK(hipMemcpyAsync(d, host, sizeof(float) * 2 * (size_t)H * W, hipMemcpyHostToDevice, c->stream));
-  f2_from_dense(c, f, d);
+  f2_from_dense(c, f, upload_dense(c, host, 2 * (size_t)H * W));
   return f;
 }
 void download_f2(of_ctx *c, const F2 &f, float *host) {
-  float *d = (float *)c->arena.alloc(sizeof(float) * 2 * (size_t)f.H * f.W);
+  float *d = new_dense<float>(c, 2 * (size_t)f.H * f.W);
   f2_to_dense(c, f, d);
-  HIPCHK(hipMemcpyAsync(host, d, sizeof(float) * 2 * (size_t)f.H * f.W, hipMemcpyDeviceToHost, c->stream));
+  download_dense(c, host, d, 2 * (size_t)f.H * f.W);
 }
 void fill_f2(of_ctx *c, const F2 &f, float v) {
   Grid2 g = grid2(f.H, f.W);
@@ -81,10 +98,8 @@ F2 init_flow(of_ctx *c, const float *init_uv, int H, int W) {
 }
 // two dense host frames of n floats each -> the arena
 void upload_frames(of_ctx *c, const float *im1, const float *im2, size_t n, float **d1, float **d2) {
-  *d1 = (float *)c->arena.alloc(sizeof(float) * n);
-  *d2 = (float *)c->arena.alloc(sizeof(float) * n);
-  HIPCHK(hipMemcpyAsync(*d1, im1, sizeof(float) * n, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(*d2, im2, sizeof(float) * n, hipMemcpyHostToDevice, c->stream));
+  *d1 = upload_dense(c, im1, n);
+  *d2 = upload_dense(c, im2, n);
 }
 
 // ---- global scale_image over all planes of an image ------------------------

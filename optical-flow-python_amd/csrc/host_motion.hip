@@ -19,12 +19,7 @@ void check_stab_opts(const of_stab_opts *o) {
   check_motion_opts(&o->fit);
   REQUIRE(o->radius >= 1 && o->radius <= 30, OF_EINVAL, "stabiliser radius must be 1..30");
   REQUIRE(std::isfinite(o->sigma_t) && o->sigma_t > 0, OF_EINVAL, "sigma_t must be finite and > 0");
-  REQUIRE(std::isfinite(o->alpha1) && std::isfinite(o->alpha2) && o->alpha1 >= 0 && o->alpha2 >= 0, OF_EINVAL,
-          "alpha1 and alpha2 must be finite and >= 0");
-}
-void check_motion_frame(int H, int W) {
-  REQUIRE(H > 0 && W > 0, OF_EINVAL, "bad arguments");
-  REQUIRE((size_t)H * W < ((size_t)1 << 31), OF_ENOTSUP, "global motion takes H * W < 2^31");
+  check_alphas(o->alpha1, o->alpha2);
 }
 
 // th in normalised coordinates -> the pixel-coordinate matrix
@@ -94,15 +89,15 @@ void fit_motion_dev(of_ctx *c, const F2 &f, const float *dw, const uint8_t *ds, 
 // device-resident frame (dense H x W x C) through the matrix A into the host buffers
 void warp_affine_dev(of_ctx *c, const float *dim, int H, int W, int C, const double A[6], float *out, uint8_t *valid) {
   const size_t px = (size_t)H * W;
-  float *dout = (float *)c->arena.alloc(sizeof(float) * px * C);
-  uint8_t *dv = valid ? (uint8_t *)c->arena.alloc(px) : nullptr;
+  float *dout = new_dense<float>(c, px * C);
+  uint8_t *dv = new_dense<uint8_t>(c, px, valid);
   AffineMat M;
   for (int k = 0; k < 6; ++k) M.a[k] = A[k];
   c->cur_px = (double)px;
   const Grid2 g = grid2(H, W);
   launch(c, "warp_affine", k_warp_affine, g.grid, g.block, 0, dim, C, M, H, W, dout, dv);
-  HIPCHK(hipMemcpyAsync(out, dout, sizeof(float) * px * C, hipMemcpyDeviceToHost, c->stream));
-  if (valid) HIPCHK(hipMemcpyAsync(valid, dv, px, hipMemcpyDeviceToHost, c->stream));
+  download_dense(c, out, dout, px * C);
+  download_dense(c, valid, dv, px);
   HIPCHK(hipStreamSynchronize(c->stream));
 }
 
@@ -164,17 +159,6 @@ Mat6 stab_smooth(const Stabilizer *s, int t) {
   return S;
 }
 
-void stabilizer_free(of_ctx *c) {
-  Stabilizer *s = c->stab;
-  if (!s) return;
-  hipSetDevice(c->device);
-  if (c->stream) hipStreamSynchronize(c->stream);
-  for (float *p : s->frame)
-    if (p) hipFree(p);
-  delete s;
-  c->stab = nullptr;
-}
-
 // frame t of the session warped onto the smoothed path, into the host buffers
 void stab_emit(of_ctx *c, Stabilizer *s, int t, float *out, uint8_t *out_valid, double *out_transform,
                int32_t *degenerate) {
@@ -184,7 +168,7 @@ void stab_emit(of_ctx *c, Stabilizer *s, int t, float *out, uint8_t *out_valid, 
   Mat6 inv = MAT6_I;
   if (mat6_invertible(S)) inv = mat6_inv(S);
   else *degenerate |= 4;
-  warp_affine_dev(c, s->frame[t % (s->opt.radius + 1)], s->H, s->W, s->C, inv.a, out, out_valid);
+  warp_affine_dev(c, s->frame[t % s->frame.size()], s->H, s->W, s->C, inv.a, out, out_valid);
   // motions before t + 1 - radius are not needed again
   while (s->motion0 < t + 1 - s->opt.radius && !s->motion.empty()) {
     s->motion.pop_front();
@@ -200,29 +184,19 @@ int of_fit_motion(of_ctx *c, const float *uv, int H, int W, const float *weight,
                   const of_motion_opts *o, of_motion_fit *out, float *out_inlier) {
   API_BEGIN(c)
   REQUIRE(uv && out, OF_EINVAL, "bad arguments");
-  check_motion_frame(H, W);
+  check_frame(H, W, "global motion");
   check_motion_opts(o);
   const size_t px = (size_t)H * W;
   if (weight)
     for (size_t k = 0; k < px; ++k)
       REQUIRE(std::isfinite(weight[k]) && weight[k] >= 0, OF_EINVAL, "weight must be finite and >= 0 everywhere");
   const F2 f = upload_f2(c, uv, H, W);
-  float *dw = nullptr, *dinl = nullptr;
-  uint8_t *ds = nullptr;
-  if (weight) {
-    dw = (float *)c->arena.alloc(sizeof(float) * px);
-    HIPCHK(hipMemcpyAsync(dw, weight, sizeof(float) * px, hipMemcpyHostToDevice, c->stream));
-  }
-  if (state) {
-    ds = (uint8_t *)c->arena.alloc(px);
-    HIPCHK(hipMemcpyAsync(ds, state, px, hipMemcpyHostToDevice, c->stream));
-  }
-  if (out_inlier) dinl = (float *)c->arena.alloc(sizeof(float) * px);
+  float *dw = upload_dense(c, weight, px);
+  uint8_t *ds = upload_dense(c, state, px);
+  float *dinl = new_dense<float>(c, px, out_inlier);
   fit_motion_dev(c, f, dw, ds, *o, out, dinl);
-  if (out_inlier) {
-    HIPCHK(hipMemcpyAsync(out_inlier, dinl, sizeof(float) * px, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-  }
+  download_dense(c, out_inlier, dinl, px);
+  if (out_inlier) HIPCHK(hipStreamSynchronize(c->stream));
   API_END(c)
 }
 
@@ -230,63 +204,31 @@ int of_warp_affine(of_ctx *c, const float *im, int H, int W, int C, const double
   API_BEGIN(c)
   REQUIRE(im && A && out, OF_EINVAL, "bad arguments");
   REQUIRE(C >= 1 && C <= OF_MAX_NC, OF_EINVAL, "images must have 1 to 4 channels");
-  check_motion_frame(H, W);
+  check_frame(H, W, "global motion");
   const size_t px = (size_t)H * W;
-  float *dim = (float *)c->arena.alloc(sizeof(float) * px * C);
-  HIPCHK(hipMemcpyAsync(dim, im, sizeof(float) * px * C, hipMemcpyHostToDevice, c->stream));
-  warp_affine_dev(c, dim, H, W, C, A, out, valid);
+  warp_affine_dev(c, upload_dense(c, im, px * C), H, W, C, A, out, valid);
   API_END(c)
 }
 
 int of_stab_open(of_ctx *c, const of_params *P, int H, int W, int C, const of_stab_opts *o) {
   API_BEGIN(c)
-  REQUIRE(!c->stab, OF_EINVAL, "a stabiliser is open on this context (of_stab_close first)");
-  REQUIRE(P, OF_EINVAL, "bad arguments");
-  REQUIRE(C == 1 || C == 3, OF_EINVAL, "frames must be (H,W) or (H,W,3)");
-  check_motion_frame(H, W);
-  check_stab_opts(o);
-  check_params(P);
-  Stabilizer *s = new Stabilizer();
-  c->stab = s;
-  try {
-    s->H = H;
-    s->W = W;
-    s->C = C;
-    s->P = *P;
-    s->opt = *o;
-    s->frame.assign(o->radius + 1, nullptr);
-    const size_t fb = sizeof(float) * (size_t)H * W * C;
-    for (float *&p : s->frame) {
-      HIPCHK(hipMalloc(&p, fb));
-      s->bytes += fb;
-    }
-  } catch (...) {
-    stabilizer_free(c);
-    throw;
-  }
+  session_open<Stabilizer>(c, SES_STAB, P, H, W, C, o, check_stab_opts,
+                           [&](Stabilizer *s) { s->alloc_frames(o->radius + 1); });
   API_END(c)
 }
 
 int of_stab_push(of_ctx *c, const float *frame, float *out, uint8_t *out_valid, double *out_transform,
                  double *out_motion, int32_t *degenerate, int32_t *out_index) {
   API_BEGIN(c)
-  Stabilizer *s = c->stab;
-  REQUIRE(s, OF_EINVAL, "no stabiliser is open on this context (of_stab_open first)");
+  Stabilizer *s = session_get<Stabilizer>(c, SES_STAB);
   REQUIRE(frame && out && degenerate && out_index, OF_EINVAL, "bad arguments");
-  REQUIRE(!s->flushed, OF_EINVAL, "the stabiliser has been flushed (of_stab_close, then open again)");
-  const int H = s->H, W = s->W, C = s->C, R = s->opt.radius, k = s->frames;
-  const size_t px = (size_t)H * W;
-  float *cur = s->frame[k % (R + 1)];
-  HIPCHK(hipMemcpyAsync(cur, frame, sizeof(float) * px * C, hipMemcpyHostToDevice, c->stream));
+  session_not_flushed(s, SES_STAB);
   *degenerate = 0;
-  if (k > 0) {
-    of_params P = s->P;
-    F2 uf = init_flow(c, nullptr, H, W), ub = init_flow(c, nullptr, H, W);
-    uint8_t *sf = (uint8_t *)c->arena.alloc(px);
-    estimate_bidir_dev(c, &P, s->frame[(k - 1) % (R + 1)], cur, H, W, C, uf, ub, s->opt.alpha1, s->opt.alpha2, sf,
-                       nullptr, nullptr, nullptr);
+  uint8_t *sf = new_dense<uint8_t>(c, (size_t)s->H * s->W, s->frames > 0);
+  const PushPair p = session_push(c, s, frame, s->opt.alpha1, s->opt.alpha2, sf, nullptr, nullptr, nullptr);
+  if (s->frames > 0) {
     of_motion_fit fit;
-    fit_motion_dev(c, uf, nullptr, sf, s->opt.fit, &fit, nullptr);
+    fit_motion_dev(c, p.fw, nullptr, sf, s->opt.fit, &fit, nullptr);
     Mat6 M;
     for (int e = 0; e < 6; ++e) M.a[e] = fit.matrix[e];
     *degenerate = fit.degenerate;
@@ -298,12 +240,11 @@ int of_stab_push(of_ctx *c, const float *frame, float *out, uint8_t *out_valid, 
     if (out_motion)
       for (int e = 0; e < 6; ++e) out_motion[e] = M.a[e];
   }
-  s->frames = k + 1;
   *out_index = -1;
-  if (k >= R) {
-    stab_emit(c, s, k - R, out, out_valid, out_transform, degenerate);
-    s->next_out = k - R + 1;
-    *out_index = k - R;
+  const int t = session_next_emit(s, s->opt.radius, false);
+  if (t >= 0) {
+    stab_emit(c, s, t, out, out_valid, out_transform, degenerate);
+    *out_index = t;
   } else {
     HIPCHK(hipStreamSynchronize(c->stream));  // the caller's frame has been read
   }
@@ -313,24 +254,18 @@ int of_stab_push(of_ctx *c, const float *frame, float *out, uint8_t *out_valid, 
 int of_stab_flush(of_ctx *c, float *out, uint8_t *out_valid, double *out_transform, int32_t *degenerate,
                   int32_t *out_index) {
   API_BEGIN(c)
-  Stabilizer *s = c->stab;
-  REQUIRE(s, OF_EINVAL, "no stabiliser is open on this context (of_stab_open first)");
+  Stabilizer *s = session_get<Stabilizer>(c, SES_STAB);
   REQUIRE(out && degenerate && out_index, OF_EINVAL, "bad arguments");
-  s->flushed = true;
   *degenerate = 0;
   *out_index = -1;
-  if (s->next_out < s->frames) {
-    stab_emit(c, s, s->next_out, out, out_valid, out_transform, degenerate);
-    *out_index = s->next_out++;
+  const int t = session_next_emit(s, s->opt.radius, true);
+  if (t >= 0) {
+    stab_emit(c, s, t, out, out_valid, out_transform, degenerate);
+    *out_index = t;
   }
   API_END(c)
 }
 
-int of_stab_close(of_ctx *c) {
-  if (!c) return OF_EINVAL;
-  if (!c->stab) return fail(c, OfError{OF_EINVAL, "no stabiliser is open on this context (of_stab_open first)"});
-  stabilizer_free(c);
-  return OF_OK;
-}
+int of_stab_close(of_ctx *c) { return session_close(c, SES_STAB); }
 
 }  // extern "C"

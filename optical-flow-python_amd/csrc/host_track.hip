@@ -10,10 +10,6 @@ void check_track_opts(const of_track_opts *o) {
   for (double v : {o->alpha1, o->alpha2, o->beta1, o->beta2, o->min_eig})
     REQUIRE(std::isfinite(v) && v >= 0, OF_EINVAL, "alpha1, alpha2, beta1, beta2 and min_eig must be finite and >= 0");
 }
-void check_track_frame(int H, int W) {
-  REQUIRE(H > 0 && W > 0, OF_EINVAL, "bad arguments");
-  REQUIRE((size_t)H * W < ((size_t)1 << 31), OF_ENOTSUP, "point tracking takes H * W < 2^31");
-}
 
 inline dim3 track_grid(int n) { return dim3((unsigned)((n + TRK_BLOCK - 1) / TRK_BLOCK)); }
 
@@ -78,24 +74,6 @@ Img track_gray(of_ctx *c, const float *frame, int H, int W, int C) {
   return view(gray, 0, 1);
 }
 
-void tracker_free(of_ctx *c) {
-  Tracker *t = c->trk;
-  if (!t) return;
-  hipSetDevice(c->device);
-  if (c->stream) hipStreamSynchronize(c->stream);
-  for (void *p : {(void *)t->frame[0], (void *)t->frame[1], (void *)t->xy, (void *)t->status, (void *)t->start,
-                  (void *)t->occ, (void *)t->flags, (void *)t->bcnt})
-    if (p) hipFree(p);
-  delete t;
-  c->trk = nullptr;
-}
-
-template <typename T>
-void tracker_alloc(Tracker *t, T **p, size_t count) {
-  HIPCHK(hipMalloc(p, sizeof(T) * count));
-  t->bytes += sizeof(T) * count;
-}
-
 }  // namespace
 
 extern "C" {
@@ -104,17 +82,15 @@ int of_track_advance(of_ctx *c, const float *fw, const float *bw, int H, int W, 
                      const float *xy_in, const uint8_t *status_in, float *xy_out, uint8_t *status_out) {
   API_BEGIN(c)
   REQUIRE(fw && bw && xy_in && status_in && xy_out && status_out && n >= 1, OF_EINVAL, "bad arguments");
-  check_track_frame(H, W);
+  check_frame(H, W, "point tracking");
   check_track_opts(o);
   REQUIRE(n <= (1 << 24), OF_EINVAL, "at most 2^24 tracks");
   F2 f = upload_f2(c, fw, H, W), b = upload_f2(c, bw, H, W);
-  float2 *dxy = (float2 *)c->arena.alloc(sizeof(float2) * n);
-  uint8_t *dst = (uint8_t *)c->arena.alloc(n);
-  HIPCHK(hipMemcpyAsync(dxy, xy_in, sizeof(float2) * n, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(dst, status_in, n, hipMemcpyHostToDevice, c->stream));
+  float2 *dxy = upload_dense(c, (const float2 *)xy_in, n);
+  uint8_t *dst = upload_dense(c, status_in, n);
   track_advance_dev(c, f, b, *o, n, dxy, dst, dxy, dst);
-  HIPCHK(hipMemcpyAsync(xy_out, dxy, sizeof(float2) * n, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipMemcpyAsync(status_out, dst, n, hipMemcpyDeviceToHost, c->stream));
+  download_dense(c, (float2 *)xy_out, dxy, n);
+  download_dense(c, status_out, dst, n);
   HIPCHK(hipStreamSynchronize(c->stream));
   API_END(c)
 }
@@ -123,24 +99,18 @@ int of_track_seed(of_ctx *c, const float *gray, int H, int W, const of_track_opt
                   const float *xy, const uint8_t *status, int32_t *n_new, int32_t *n_dropped, float *xy_new) {
   API_BEGIN(c)
   REQUIRE(gray && n_new && n_dropped && xy_new && frame >= 0, OF_EINVAL, "bad arguments");
-  check_track_frame(H, W);
+  check_frame(H, W, "point tracking");
   check_track_opts(o);
   REQUIRE(n >= 0 && n <= o->max_tracks && (n == 0 || (xy && status)), OF_EINVAL,
           "the table must hold 0..max_tracks tracks");
   const SeedGrid g = seed_grid(H, W, o->step);
   const int room = std::min(o->max_tracks - n, g.ncells);
   Img G = upload_new_img(c, gray, H, W, 1);
-  float2 *dxy = nullptr;
-  uint8_t *dst = nullptr;
-  if (n > 0) {
-    dxy = (float2 *)c->arena.alloc(sizeof(float2) * n);
-    dst = (uint8_t *)c->arena.alloc(n);
-    HIPCHK(hipMemcpyAsync(dxy, xy, sizeof(float2) * n, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(dst, status, n, hipMemcpyHostToDevice, c->stream));
-  }
-  uint8_t *occ = (uint8_t *)c->arena.alloc(g.ncells), *flags = (uint8_t *)c->arena.alloc(g.ncells);
-  int *bcnt = (int *)c->arena.alloc(sizeof(int) * (g.nb + 1));
-  float2 *dnew = (float2 *)c->arena.alloc(sizeof(float2) * std::max(room, 1));
+  float2 *dxy = upload_dense(c, n > 0 ? (const float2 *)xy : nullptr, n);
+  uint8_t *dst = upload_dense(c, n > 0 ? status : nullptr, n);
+  uint8_t *occ = new_dense<uint8_t>(c, g.ncells), *flags = new_dense<uint8_t>(c, g.ncells);
+  int *bcnt = new_dense<int>(c, g.nb + 1);
+  float2 *dnew = new_dense<float2>(c, std::max(room, 1));
   const int total = track_seed_dev(c, G, *o, frame, n, dxy, dst, occ, flags, bcnt, room, dnew, nullptr, nullptr);
   *n_new = std::min(total, room);
   *n_dropped = total - *n_new;
@@ -150,65 +120,39 @@ int of_track_seed(of_ctx *c, const float *gray, int H, int W, const of_track_opt
 
 int of_tracks_open(of_ctx *c, const of_params *P, int H, int W, int C, const of_track_opts *o) {
   API_BEGIN(c)
-  REQUIRE(!c->trk, OF_EINVAL, "a point tracker is open on this context (of_tracks_close first)");
-  REQUIRE(P, OF_EINVAL, "bad arguments");
-  REQUIRE(C == 1 || C == 3, OF_EINVAL, "frames must be (H,W) or (H,W,3)");
-  check_track_frame(H, W);
-  check_track_opts(o);
-  check_params(P);
-  Tracker *t = new Tracker();
-  c->trk = t;
-  try {
-    t->H = H;
-    t->W = W;
-    t->C = C;
-    t->P = *P;
-    t->opt = *o;
+  session_open<Tracker>(c, SES_TRACK, P, H, W, C, o, check_track_opts, [&](Tracker *t) {
     const SeedGrid g = seed_grid(H, W, o->step);
-    const size_t px = (size_t)H * W;
-    tracker_alloc(t, &t->frame[0], px * C);
-    tracker_alloc(t, &t->frame[1], px * C);
-    tracker_alloc(t, &t->xy, (size_t)o->max_tracks);
-    tracker_alloc(t, &t->status, (size_t)o->max_tracks);
-    tracker_alloc(t, &t->start, (size_t)o->max_tracks);
-    tracker_alloc(t, &t->occ, (size_t)g.ncells);
-    tracker_alloc(t, &t->flags, (size_t)g.ncells);
-    tracker_alloc(t, &t->bcnt, (size_t)g.nb + 1);
-  } catch (...) {
-    tracker_free(c);
-    throw;
-  }
+    t->alloc_frames(2);
+    t->xy = t->alloc<float2>((size_t)o->max_tracks);
+    t->status = t->alloc<uint8_t>((size_t)o->max_tracks);
+    t->start = t->alloc<int32_t>((size_t)o->max_tracks);
+    t->occ = t->alloc<uint8_t>((size_t)g.ncells);
+    t->flags = t->alloc<uint8_t>((size_t)g.ncells);
+    t->bcnt = t->alloc<int>((size_t)g.nb + 1);
+  });
   API_END(c)
 }
 
 int of_tracks_push(of_ctx *c, const float *frame, float *out_fw, float *out_bw, uint8_t *state_fw, uint8_t *state_bw,
                    int32_t *n_tracks, int32_t *n_new, int32_t *n_dropped, of_stats *sf, of_stats *sb) {
   API_BEGIN(c)
-  Tracker *t = c->trk;
-  REQUIRE(t, OF_EINVAL, "no point tracker is open on this context (of_tracks_open first)");
+  Tracker *t = session_get<Tracker>(c, SES_TRACK);
   REQUIRE(frame, OF_EINVAL, "bad arguments");
   const int H = t->H, W = t->W, C = t->C;
   const size_t px = (size_t)H * W;
-  float *cur = t->frame[t->frames & 1], *prev = t->frame[(t->frames & 1) ^ 1];
-  HIPCHK(hipMemcpyAsync(cur, frame, sizeof(float) * px * C, hipMemcpyHostToDevice, c->stream));
+  uint8_t *dsf = new_dense<uint8_t>(c, px, state_fw && t->frames > 0);
+  uint8_t *dsb = new_dense<uint8_t>(c, px, state_bw && t->frames > 0);
+  const PushPair p = session_push(c, t, frame, t->opt.alpha1, t->opt.alpha2, dsf, dsb, sf, sb);
   if (t->frames > 0) {
-    if (sf) memset(sf, 0, sizeof(*sf));
-    if (sb) memset(sb, 0, sizeof(*sb));
-    const WallClock wall;
-    of_params P = t->P;
-    F2 uf = init_flow(c, nullptr, H, W), ub = init_flow(c, nullptr, H, W);
-    uint8_t *dsf = state_fw ? (uint8_t *)c->arena.alloc(px) : nullptr;
-    uint8_t *dsb = state_bw ? (uint8_t *)c->arena.alloc(px) : nullptr;
-    estimate_bidir_dev(c, &P, prev, cur, H, W, C, uf, ub, t->opt.alpha1, t->opt.alpha2, dsf, dsb, sf, sb);
-    if (t->n > 0) track_advance_dev(c, uf, ub, t->opt, t->n, t->xy, t->status, t->xy, t->status);
-    if (out_fw) download_f2(c, uf, out_fw);
-    if (out_bw) download_f2(c, ub, out_bw);
-    if (state_fw) HIPCHK(hipMemcpyAsync(state_fw, dsf, px, hipMemcpyDeviceToHost, c->stream));
-    if (state_bw) HIPCHK(hipMemcpyAsync(state_bw, dsb, px, hipMemcpyDeviceToHost, c->stream));
+    if (t->n > 0) track_advance_dev(c, p.fw, p.bw, t->opt, t->n, t->xy, t->status, t->xy, t->status);
+    if (out_fw) download_f2(c, p.fw, out_fw);
+    if (out_bw) download_f2(c, p.bw, out_bw);
+    download_dense(c, state_fw, dsf, px);
+    download_dense(c, state_bw, dsb, px);
     HIPCHK(hipStreamSynchronize(c->stream));
-    if (sf) sf->total_ms = wall.ms();
+    if (sf) sf->total_ms = p.wall.ms();
   }
-  const Img gray = track_gray(c, cur, H, W, C);
+  const Img gray = track_gray(c, p.cur, H, W, C);
   const int room = t->opt.max_tracks - t->n;
   const int total = track_seed_dev(c, gray, t->opt, t->frames, t->n, t->xy, t->status, t->occ, t->flags, t->bcnt, room,
                                    t->xy + t->n, t->status + t->n, t->start + t->n);
@@ -224,8 +168,7 @@ int of_tracks_push(of_ctx *c, const float *frame, float *out_fw, float *out_bw, 
 int of_tracks_read(of_ctx *c, int first, int n, float *xy, uint8_t *status, int32_t *start) {
   if (!c) return OF_EINVAL;
   try {
-    Tracker *t = c->trk;
-    REQUIRE(t, OF_EINVAL, "no point tracker is open on this context (of_tracks_open first)");
+    Tracker *t = session_get<Tracker>(c, SES_TRACK);
     REQUIRE(first >= 0 && n >= 0 && first <= t->n && n <= t->n - first, OF_EINVAL, "tracks out of range");
     if (n == 0) return OF_OK;
     HIPCHK(hipSetDevice(c->device));
@@ -238,11 +181,6 @@ int of_tracks_read(of_ctx *c, int first, int n, float *xy, uint8_t *status, int3
   API_CATCH(c)
 }
 
-int of_tracks_close(of_ctx *c) {
-  if (!c) return OF_EINVAL;
-  if (!c->trk) return fail(c, OfError{OF_EINVAL, "no point tracker is open on this context (of_tracks_open first)"});
-  tracker_free(c);
-  return OF_OK;
-}
+int of_tracks_close(of_ctx *c) { return session_close(c, SES_TRACK); }
 
 }  // extern "C"

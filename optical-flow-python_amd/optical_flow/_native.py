@@ -272,6 +272,10 @@ def dptr(a):
     return None if a is None else a.ctypes.data_as(_dp)
 
 
+def i32ptr(a):
+    return None if a is None else a.ctypes.data_as(_i32p)
+
+
 def data_weight(w, H, W):
     """The per-pixel data-term weight as the C ABI takes it (include/optflow.h,
     "Per-pixel data-term weights"): contiguous (H, W) float32, or None.

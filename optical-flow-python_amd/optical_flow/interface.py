@@ -11,7 +11,7 @@ import numpy as np
 from optical_flow import _abi
 from optical_flow import _native as nat
 from optical_flow.methods.base import progress_printer
-from optical_flow.methods.config import load_of_method
+from optical_flow._session import Closing, method_params
 
 
 def estimate_flow(im1, im2, method='classic+nl-fast', params=None, gt=None, data_weight=None):
@@ -35,9 +35,7 @@ def estimate_flow(im1, im2, method='classic+nl-fast', params=None, gt=None, data
     weight raises NotImplementedError."""
     im1 = np.asarray(im1, dtype=float)
     im2 = np.asarray(im2, dtype=float)
-    ope = load_of_method(method)
-    if params is not None:
-        ope.parse_input_parameter(params)
+    ope, P = method_params(method, params)
     H, W = im1.shape[:2]
     wgt = nat.data_weight(data_weight, H, W)
     if im1.ndim == 3 and im1.shape[2] < 3:
@@ -52,8 +50,6 @@ def estimate_flow(im1, im2, method='classic+nl-fast', params=None, gt=None, data
         Cc = 3
     else:
         a, b, Cc = nat.f32(im1), nat.f32(im2), 1
-    P = ope.to_params()
-    P.guide_mode = int(ope._METHOD == 'classic_nl' and ope.color_images is not None)
     out = np.empty((2, H, W), dtype=np.float32)
     st = _abi.OfStats()
     ctx = nat.context()
@@ -91,15 +87,11 @@ def estimate_flow_bidirectional(im1, im2, method='classic+nl-fast', params=None,
         bw = estimate_flow(im2, im1, method, params)
         return BidirectionalFlow(fw, bw, forward_backward_check(fw, bw, alpha1, alpha2),
                                  forward_backward_check(bw, fw, alpha1, alpha2))
-    ope = load_of_method(method)
-    if params is not None:
-        ope.parse_input_parameter(params)
+    ope, P = method_params(method, params)
     if im1.ndim == 3:
         a, b, Cc = nat.f32(im1[:, :, :3]), nat.f32(im2[:, :, :3]), 3
     else:
         a, b, Cc = nat.f32(im1), nat.f32(im2), 1
-    P = ope.to_params()
-    P.guide_mode = int(ope._METHOD == 'classic_nl' and ope.color_images is not None)
     out_f = np.empty((2, H, W), dtype=np.float32)
     out_b = np.empty((2, H, W), dtype=np.float32)
     occ_f = np.empty((H, W), dtype=np.uint8)
@@ -176,11 +168,7 @@ def interpolate_frames(im1, im2, t=0.5, method='classic+nl-fast', params=None, f
                                            nat.ptr(nat.planar(bw)), float(alpha1), float(alpha2), n, nat.dptr(ts),
                                            nat.ptr(out), nat.ptr(ut), nat.u8ptr(info)))
     else:
-        ope = load_of_method(method)
-        if params is not None:
-            ope.parse_input_parameter(params)
-        P = ope.to_params()
-        P.guide_mode = int(ope._METHOD == 'classic_nl' and ope.color_images is not None)
+        ope, P = method_params(method, params)
         st_f, st_b = _abi.OfStats(), _abi.OfStats()
         ctx = nat.context()
         fn, flags = progress_printer(ope, None)
@@ -233,11 +221,7 @@ def estimate_flow_batch(im1s, im2s, method='classic+nl-fast', params=None, lanes
             raise ValueError("all frames of a batch must share one shape")
     a = [np.ascontiguousarray(x) for x in a]
     b = [np.ascontiguousarray(x) for x in b]
-    ope = load_of_method(method)
-    if params is not None:
-        ope.parse_input_parameter(params)
-    P = ope.to_params()
-    P.guide_mode = int(ope._METHOD == 'classic_nl' and ope.color_images is not None)
+    P = method_params(method, params)[1]
     n = len(a)
     outs = [np.empty((2, H, W), dtype=np.float32) for _ in range(n)]
     vp = C.c_void_p
@@ -249,7 +233,7 @@ def estimate_flow_batch(im1s, im2s, method='classic+nl-fast', params=None, lanes
     return [nat.interleaved(o) for o in outs]
 
 
-class PairStream:
+class PairStream(Closing):
     """Streaming estimate_flow over uint8 frame pairs of one shape: a pool of
     `lanes` GPU pipelines (of_pairs_open, include/optflow.h) on a context of
     its own takes pairs as they are submitted, so host work between
@@ -264,11 +248,7 @@ class PairStream:
     def __init__(self, H, W, channels=3, method='classic+nl-fast', params=None, lanes=4, device=0):
         if channels not in (1, 3):
             raise ValueError("channels must be 1 (gray) or 3 (RGB)")
-        ope = load_of_method(method)
-        if params is not None:
-            ope.parse_input_parameter(params)
-        P = ope.to_params()
-        P.guide_mode = int(ope._METHOD == 'classic_nl' and ope.color_images is not None)
+        P = method_params(method, params)[1]
         self.shape = (H, W, 3) if channels == 3 else (H, W)
         self.H, self.W, self.channels = H, W, channels
         self._ctx = nat.Context(device)
@@ -316,18 +296,6 @@ class PairStream:
                 self._ctx.close()
                 self._ctx = None
                 self._live.clear()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def _preprocess(im1, im2):

@@ -17,9 +17,7 @@ import numpy as np
 
 from optical_flow import _abi
 from optical_flow import _native as nat
-from optical_flow.methods.config import load_of_method
-from optical_flow.temporal import _flow, _number, _planar32, _state
-from optical_flow.tracking import _frame_size, _i32ptr, _int_in
+from optical_flow._session import DelayedSession, _flow, _frame_size, _int_in, _number, _planar32, _state
 
 MotionFit = namedtuple("MotionFit", "matrix theta cutoff support rms passes degenerate inliers")
 MotionFit.__doc__ = """Result of fit_motion: `matrix` (2, 3) maps a point (column, row) of the
@@ -101,7 +99,7 @@ def warp_affine(im, matrix, return_valid=False):
     return (out, valid) if return_valid else out
 
 
-class Stabilizer:
+class Stabilizer(DelayedSession):
     """Video stabiliser over frames of one shape, (H, W) or (H, W, 3): the last
     radius + 1 frames stay on the GPU (of_stab_open / _push / _flush).
 
@@ -127,37 +125,26 @@ class Stabilizer:
     package may run between pushes), or a `context` (_native.Context) of your
     own."""
 
+    _PREFIX, _NAME = "of_stab_", "stabiliser"
+
     def __init__(self, shape, method='classic+nl-fast', params=None, model='similarity', radius=8, sigma_t=3.0,
                  iters=10, kappa=2.0, decay=0.5, c_min=0.5, alpha1=0.01, alpha2=0.5, context=None):
-        self._ctx = None
-        shape = tuple(int(s) for s in shape)
-        if len(shape) not in (2, 3) or (len(shape) == 3 and shape[2] != 3):
-            raise ValueError(f"shape must be (H, W) or (H, W, 3), got {shape}")
-        H, W = shape[:2]
-        _frame_size(H, W)
-        self._opts = _abi.OfStabOpts(_motion_opts(model, iters, kappa, decay, c_min),
-                                     _int_in("radius", radius, 1, _abi.STAB_MAX_RADIUS), 0,
-                                     _number("sigma_t", sigma_t, True), _number("alpha1", alpha1, False),
-                                     _number("alpha2", alpha2, False))
-        ope = load_of_method(method)
-        if params is not None:
-            ope.parse_input_parameter(params)
-        P = ope.to_params()
-        P.guide_mode = int(ope._METHOD == 'classic_nl' and ope.color_images is not None)
-        self.shape, self.H, self.W, self.channels = shape, H, W, 3 if len(shape) == 3 else 1
+        super().__init__(shape, method, params, lambda H, W: _abi.OfStabOpts(
+            _motion_opts(model, iters, kappa, decay, c_min), _int_in("radius", radius, 1, _abi.STAB_MAX_RADIUS), 0,
+            _number("sigma_t", sigma_t, True), _number("alpha1", alpha1, False), _number("alpha2", alpha2, False)),
+            context)
         self.radius = self._opts.radius
-        self.frames = 0
         self.last_motion = self.last_transform = self.last_valid = None
         self.last_degenerate = 0
-        ctx = nat.context() if context is None else context
-        ctx.check(ctx.lib.of_stab_open(ctx.handle, C.byref(P), H, W, self.channels, C.byref(self._opts)))
-        self._ctx = ctx
 
-    def _buffers(self):
-        return (np.empty(self.shape, dtype=np.float32), np.empty((self.H, self.W), dtype=np.uint8),
-                np.empty(6, dtype=np.float64), np.zeros(1, dtype=np.int32), np.full(1, -1, dtype=np.int32))
-
-    def _result(self, out, valid, S, deg, idx):
+    def _step(self, call, *args, motion=None):
+        out = np.empty(self.shape, dtype=np.float32)
+        valid = np.empty((self.H, self.W), dtype=np.uint8)
+        S = np.empty(6, dtype=np.float64)
+        deg, idx = np.zeros(1, dtype=np.int32), np.full(1, -1, dtype=np.int32)
+        call(*args, nat.ptr(out), nat.u8ptr(valid), nat.dptr(S), *([] if motion is None else [nat.dptr(motion)]),
+             nat.i32ptr(deg), nat.i32ptr(idx))
+        self.last_motion = None if motion is None else motion.reshape(2, 3)
         self.last_degenerate = int(deg[0])
         if idx[0] < 0:
             return None
@@ -168,54 +155,13 @@ class Stabilizer:
         """The next frame.  Returns (index, frame) of the stabilised frame that
         became complete, float64 in the input's shape, or None while fewer
         than radius + 1 frames have been pushed."""
-        if self._ctx is None:
-            raise ValueError("the stabiliser is closed")
-        f = np.asarray(frame)
-        if f.shape != self.shape or f.dtype.kind not in "fiu":
-            raise ValueError(f"frames must be {self.shape} arrays of numbers, got {f.dtype} {f.shape}")
-        f = nat.f32(np.asarray(f, dtype=float))
-        out, valid, S, deg, idx = self._buffers()
-        M = np.empty(6, dtype=np.float64)
-        ctx = self._ctx
-        ctx.check(ctx.lib.of_stab_push(ctx.handle, nat.ptr(f), nat.ptr(out), nat.u8ptr(valid), nat.dptr(S),
-                                       nat.dptr(M), _i32ptr(deg), _i32ptr(idx)))
-        self.last_motion = M.reshape(2, 3) if self.frames > 0 else None
-        self.frames += 1
-        return self._result(out, valid, S, deg, idx)
-
-    def flush(self):
-        """Yields (index, frame) for the frames still pending at the end of
-        the clip, smoothed over the neighbours that exist.  No push after it."""
-        if self._ctx is None:
-            raise ValueError("the stabiliser is closed")
-        ctx = self._ctx
-        while True:
-            out, valid, S, deg, idx = self._buffers()
-            ctx.check(ctx.lib.of_stab_flush(ctx.handle, nat.ptr(out), nat.u8ptr(valid), nat.dptr(S), _i32ptr(deg),
-                                            _i32ptr(idx)))
+        r = self._step(self._push, frame, motion=np.empty(6, dtype=np.float64))
+        if self.frames == 1:
             self.last_motion = None
-            r = self._result(out, valid, S, deg, idx)
-            if r is None:
-                return
-            yield r
+        return r
 
-    def close(self):
-        if self._ctx is not None:
-            ctx, self._ctx = self._ctx, None
-            if ctx.handle:
-                ctx.check(ctx.lib.of_stab_close(ctx.handle))
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _flush_step(self):
+        return self._step(self._call, "flush")
 
 
 def stabilize_frames(frames, method='classic+nl-fast', model='similarity', radius=8, sigma_t=3.0, params=None,
@@ -224,18 +170,6 @@ def stabilize_frames(frames, method='classic+nl-fast', model='similarity', radiu
     frame of one shape) with a Stabilizer: returns (T, H, W[, 3]) float64; with
     `return_transforms` also the (T, 2, 3) float64 S_t each frame was moved
     by (a point of frame t lies at S_t^-1 of it in the output)."""
-    frames = [np.asarray(f) for f in frames]
-    if not frames or any(f.shape != frames[0].shape for f in frames):
-        raise ValueError("frames must be a non-empty sequence of frames of one shape")
-    out = np.empty((len(frames),) + frames[0].shape, dtype=np.float64)
-    tr = np.empty((len(frames), 2, 3), dtype=np.float64)
-    with Stabilizer(frames[0].shape, method, params, model, radius, sigma_t, iters, kappa, decay, c_min, alpha1,
-                    alpha2) as st:
-        def take(r):
-            if r is not None:
-                out[r[0]], tr[r[0]] = r[1], st.last_transform
-        for f in frames:
-            take(st.push(f))
-        for r in st.flush():
-            take(r)
+    out, tr = Stabilizer.run_clip(frames, "last_transform", method, params, model, radius, sigma_t, iters, kappa,
+                                  decay, c_min, alpha1, alpha2)
     return (out, tr) if return_transforms else out

@@ -14,15 +14,7 @@ import numpy as np
 
 from optical_flow import _abi
 from optical_flow import _native as nat
-from optical_flow.methods.config import load_of_method
-from optical_flow.tracking import _frame_size, _i32ptr, _int_in
-
-
-def _number(name, v, positive):
-    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) \
-            or (v <= 0 if positive else v < 0):
-        raise ValueError(f"{name} must be a finite number {'> 0' if positive else '>= 0'}, got {v!r}")
-    return float(v)
+from optical_flow._session import DelayedSession, _flow, _frame_size, _int_in, _number, _planar32, _state
 
 
 def _fuse_opts(sigma, radius=1, strength=4.0, patch=2, alpha1=0.01, alpha2=0.5):
@@ -34,29 +26,6 @@ def _fuse_opts(sigma, radius=1, strength=4.0, patch=2, alpha1=0.01, alpha2=0.5):
                            _int_in("patch", patch, 0, _abi.FUSE_MAX_PATCH), _number("sigma", sigma, True),
                            _number("strength", strength, True), _number("alpha1", alpha1, False),
                            _number("alpha2", alpha2, False))
-
-
-def _flow(name, f, shape=None):
-    f = np.asarray(f)
-    if f.ndim != 3 or f.shape[2] != 2 or f.dtype.kind not in "fiu" or (shape is not None and f.shape[:2] != shape):
-        want = "(H, W, 2)" if shape is None else f"{shape + (2,)}"
-        raise ValueError(f"{name} must be a {want} array of numbers, got {f.dtype} {f.shape}")
-    return f
-
-
-def _state(name, s, H, W):
-    """A forward-backward mask as contiguous (H, W) uint8, or None."""
-    if s is None:
-        return None
-    s = np.asarray(s)
-    if s.shape != (H, W) or s.dtype.kind not in "iub" or (s.size and (s.min() < 0 or s.max() > 255)):
-        raise ValueError(f"{name} must be ({H}, {W}) integers in 0..255, got {s.dtype} {s.shape}")
-    return np.ascontiguousarray(s, dtype=np.uint8)
-
-
-def _planar32(f):
-    with np.errstate(over='ignore'):
-        return nat.planar(f)
 
 
 def compose_flows(f, g, state_f=None, state_g=None, return_state=False):
@@ -141,7 +110,7 @@ def fuse_frames(center, neighbours, flows, sigma=None, states=None, strength=4.0
     return (out, wgt.astype(np.float64)) if return_weight else out
 
 
-class TemporalDenoiser:
+class TemporalDenoiser(DelayedSession):
     """Temporal denoiser over frames of one shape, (H, W) or (H, W, 3): the
     last 2 radius + 1 frames and both flows and masks of the pairs between
     them stay on the GPU (of_denoise_open / _push / _flush).
@@ -163,29 +132,20 @@ class TemporalDenoiser:
     calls of the package may run between pushes), or a `context`
     (_native.Context) of your own.  `sigma` is required."""
 
+    _PREFIX, _NAME = "of_denoise_", "denoiser"
+
     def __init__(self, shape, method='classic+nl-fast', params=None, sigma=None, radius=1, strength=4.0, patch=2,
                  alpha1=0.01, alpha2=0.5, context=None):
-        self._ctx = None
-        shape = tuple(int(s) for s in shape)
-        if len(shape) not in (2, 3) or (len(shape) == 3 and shape[2] != 3):
-            raise ValueError(f"shape must be (H, W) or (H, W, 3), got {shape}")
-        H, W = shape[:2]
-        _frame_size(H, W)
-        self._opts = _fuse_opts(sigma, radius, strength, patch, alpha1, alpha2)
-        ope = load_of_method(method)
-        if params is not None:
-            ope.parse_input_parameter(params)
-        P = ope.to_params()
-        P.guide_mode = int(ope._METHOD == 'classic_nl' and ope.color_images is not None)
-        self.shape, self.H, self.W, self.channels = shape, H, W, 3 if len(shape) == 3 else 1
+        super().__init__(shape, method, params,
+                         lambda H, W: _fuse_opts(sigma, radius, strength, patch, alpha1, alpha2), context)
         self.radius = self._opts.radius
-        self.frames = 0
         self.last_weight = None
-        ctx = nat.context() if context is None else context
-        ctx.check(ctx.lib.of_denoise_open(ctx.handle, C.byref(P), H, W, self.channels, C.byref(self._opts)))
-        self._ctx = ctx
 
-    def _result(self, out, wgt, idx):
+    def _step(self, call, *args):
+        out = np.empty(self.shape, dtype=np.float32)
+        wgt = np.empty((self.H, self.W), dtype=np.float32)
+        idx = np.full(1, -1, dtype=np.int32)
+        call(*args, nat.ptr(out), nat.ptr(wgt), nat.i32ptr(idx))
         if idx[0] < 0:
             return None
         self.last_weight = wgt.astype(np.float64)
@@ -195,53 +155,10 @@ class TemporalDenoiser:
         """The next frame.  Returns (index, frame) of the denoised frame that
         became complete, float64 in the input's shape, or None while fewer
         than radius + 1 frames have been pushed."""
-        if self._ctx is None:
-            raise ValueError("the denoiser is closed")
-        f = np.asarray(frame)
-        if f.shape != self.shape or f.dtype.kind not in "fiu":
-            raise ValueError(f"frames must be {self.shape} arrays of numbers, got {f.dtype} {f.shape}")
-        f = nat.f32(np.asarray(f, dtype=float))
-        out = np.empty(self.shape, dtype=np.float32)
-        wgt = np.empty((self.H, self.W), dtype=np.float32)
-        idx = np.full(1, -1, dtype=np.int32)
-        ctx = self._ctx
-        ctx.check(ctx.lib.of_denoise_push(ctx.handle, nat.ptr(f), nat.ptr(out), nat.ptr(wgt), _i32ptr(idx)))
-        self.frames += 1
-        return self._result(out, wgt, idx)
+        return self._step(self._push, frame)
 
-    def flush(self):
-        """Yields (index, frame) for the frames still pending at the end of
-        the clip, fused with the neighbours that exist.  No push after it."""
-        if self._ctx is None:
-            raise ValueError("the denoiser is closed")
-        ctx = self._ctx
-        while True:
-            out = np.empty(self.shape, dtype=np.float32)
-            wgt = np.empty((self.H, self.W), dtype=np.float32)
-            idx = np.full(1, -1, dtype=np.int32)
-            ctx.check(ctx.lib.of_denoise_flush(ctx.handle, nat.ptr(out), nat.ptr(wgt), _i32ptr(idx)))
-            r = self._result(out, wgt, idx)
-            if r is None:
-                return
-            yield r
-
-    def close(self):
-        if self._ctx is not None:
-            ctx, self._ctx = self._ctx, None
-            if ctx.handle:
-                ctx.check(ctx.lib.of_denoise_close(ctx.handle))
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _flush_step(self):
+        return self._step(self._call, "flush")
 
 
 def denoise_frames(frames, method='classic+nl-fast', sigma=None, radius=1, strength=4.0, patch=2, alpha1=0.01,
@@ -250,17 +167,6 @@ def denoise_frames(frames, method='classic+nl-fast', sigma=None, radius=1, stren
     of one shape) with a TemporalDenoiser: returns (T, H, W[, 3]) float64;
     with `return_weight` also the (T, H, W) float64 effective number of frames
     averaged per pixel.  `sigma` is required."""
-    frames = [np.asarray(f) for f in frames]
-    if not frames or any(f.shape != frames[0].shape for f in frames):
-        raise ValueError("frames must be a non-empty sequence of frames of one shape")
-    out = np.empty((len(frames),) + frames[0].shape, dtype=np.float64)
-    wgt = np.empty((len(frames),) + frames[0].shape[:2], dtype=np.float64)
-    with TemporalDenoiser(frames[0].shape, method, params, sigma, radius, strength, patch, alpha1, alpha2) as dn:
-        def take(r):
-            if r is not None:
-                out[r[0]], wgt[r[0]] = r[1], dn.last_weight
-        for f in frames:
-            take(dn.push(f))
-        for r in dn.flush():
-            take(r)
+    out, wgt = TemporalDenoiser.run_clip(frames, "last_weight", method, params, sigma, radius, strength, patch, alpha1,
+                                         alpha2)
     return (out, wgt) if return_weight else out

@@ -14,7 +14,7 @@ import numpy as np
 
 from optical_flow import _abi
 from optical_flow import _native as nat
-from optical_flow.methods.config import load_of_method
+from optical_flow._session import Session, _clip, _frame_size, _int_in
 
 # status of a track (of_track_advance, include/optflow.h)
 TRACK_ALIVE = _abi.OF_TRACK_ALIVE
@@ -23,18 +23,8 @@ TRACK_LEFT_FRAME = _abi.OF_TRACK_LEFT_FRAME
 TRACK_MOTION_BOUNDARY = _abi.OF_TRACK_MOTION_BOUNDARY
 
 
-def _i32ptr(a):
-    return a.ctypes.data_as(C.POINTER(C.c_int32))
-
-
 def _cells(H, W, step):
     return -(-H // step) * -(-W // step)
-
-
-def _int_in(name, v, lo, hi):
-    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
-        raise ValueError(f"{name} must be an integer in {lo}..{hi}, got {v!r}")
-    return int(v)
 
 
 def _track_opts(H, W, step=8, max_tracks=None, alpha1=0.01, alpha2=0.5, beta1=0.01, beta2=0.002, min_eig=25.0):
@@ -51,11 +41,6 @@ def _track_opts(H, W, step=8, max_tracks=None, alpha1=0.01, alpha2=0.5, beta1=0.
             raise ValueError(f"{k} must be a finite number >= 0, got {v!r}")
     return _abi.OfTrackOpts(step, max_tracks, float(alpha1), float(alpha2), float(beta1), float(beta2),
                             float(min_eig))
-
-
-def _frame_size(H, W):
-    if H <= 0 or W <= 0 or H * W >= 1 << 31:
-        raise ValueError(f"frames must be non-empty and below 2^31 pixels, got {H} x {W}")
 
 
 def _table(xy, status, allow_none):
@@ -140,8 +125,8 @@ def seed_points(gray, xy=None, status=None, step=8, max_tracks=None, min_eig=25.
     n_new, n_drop = np.zeros(1, np.int32), np.zeros(1, np.int32)
     ctx = nat.context()
     ctx.check(ctx.lib.of_track_seed(ctx.handle, nat.ptr(nat.f32(gray)), H, W, C.byref(opts), frame, n,
-                                    nat.ptr(pts if n else None), nat.u8ptr(st if n else None), _i32ptr(n_new),
-                                    _i32ptr(n_drop), nat.ptr(out)))
+                                    nat.ptr(pts if n else None), nat.u8ptr(st if n else None), nat.i32ptr(n_new),
+                                    nat.i32ptr(n_drop), nat.ptr(out)))
     new = out[:int(n_new[0])].copy()
     return (new, int(n_drop[0])) if return_dropped else new
 
@@ -150,7 +135,7 @@ TrackSnapshot = namedtuple('TrackSnapshot', ['xy', 'status', 'start', 'n_new', '
                                              'occ_forward', 'occ_backward'])
 
 
-class PointTracker:
+class PointTracker(Session):
     """Dense point tracker over frames of one shape, (H, W) or (H, W, 3): the
     track table, the previous frame and both flows of every pair stay on the
     GPU (of_tracks_open / of_tracks_push, include/optflow.h).
@@ -167,25 +152,13 @@ class PointTracker:
     package may run between pushes), or a `context` (_native.Context) of
     your own for a second tracker at the same time."""
 
+    _PREFIX, _NAME = "of_tracks_", "tracker"
+
     def __init__(self, shape, method='classic+nl-fast', params=None, step=8, max_tracks=None, min_eig=25.0,
                  alpha1=0.01, alpha2=0.5, beta1=0.01, beta2=0.002, context=None):
-        self._ctx = None
-        shape = tuple(int(s) for s in shape)
-        if len(shape) not in (2, 3) or (len(shape) == 3 and shape[2] != 3):
-            raise ValueError(f"shape must be (H, W) or (H, W, 3), got {shape}")
-        H, W = shape[:2]
-        _frame_size(H, W)
-        self._opts = _track_opts(H, W, step, max_tracks, alpha1, alpha2, beta1, beta2, min_eig)
-        ope = load_of_method(method)
-        if params is not None:
-            ope.parse_input_parameter(params)
-        P = ope.to_params()
-        P.guide_mode = int(ope._METHOD == 'classic_nl' and ope.color_images is not None)
-        self.shape, self.H, self.W, self.channels = shape, H, W, 3 if len(shape) == 3 else 1
-        self.frames = 0
-        ctx = nat.context() if context is None else context
-        ctx.check(ctx.lib.of_tracks_open(ctx.handle, C.byref(P), H, W, self.channels, C.byref(self._opts)))
-        self._ctx = ctx
+        super().__init__(shape, method, params,
+                         lambda H, W: _track_opts(H, W, step, max_tracks, alpha1, alpha2, beta1, beta2, min_eig),
+                         context)
 
     def push(self, frame, return_flows=False):
         """The next frame.  Returns a TrackSnapshot: xy (N, 2) float32, status
@@ -193,12 +166,6 @@ class PointTracker:
         n_dropped of this frame's seeding; with `return_flows` also forward,
         backward (H, W, 2) float64 and occ_forward, occ_backward (H, W) uint8
         of the pair (previous frame, this frame), None on the first push."""
-        if self._ctx is None:
-            raise ValueError("the tracker is closed")
-        f = np.asarray(frame)
-        if f.shape != self.shape or f.dtype.kind not in "fiu":
-            raise ValueError(f"frames must be {self.shape} arrays of numbers, got {f.dtype} {f.shape}")
-        f = nat.f32(np.asarray(f, dtype=float))
         H, W = self.H, self.W
         flows = return_flows and self.frames > 0
         out_f = np.empty((2, H, W), dtype=np.float32) if flows else None
@@ -206,41 +173,19 @@ class PointTracker:
         occ_f = np.empty((H, W), dtype=np.uint8) if flows else None
         occ_b = np.empty((H, W), dtype=np.uint8) if flows else None
         cnt = np.zeros(3, dtype=np.int32)
-        p = _i32ptr(cnt)
         st_f, st_b = _abi.OfStats(), _abi.OfStats()
-        ctx = self._ctx
-        ctx.check(ctx.lib.of_tracks_push(ctx.handle, nat.ptr(f), nat.ptr(out_f), nat.ptr(out_b), nat.u8ptr(occ_f),
-                                         nat.u8ptr(occ_b), p, _i32ptr(cnt[1:]), _i32ptr(cnt[2:]), C.byref(st_f),
-                                         C.byref(st_b)))
-        self.frames += 1
+        self._push(frame, nat.ptr(out_f), nat.ptr(out_b), nat.u8ptr(occ_f), nat.u8ptr(occ_b), nat.i32ptr(cnt),
+                   nat.i32ptr(cnt[1:]), nat.i32ptr(cnt[2:]), C.byref(st_f), C.byref(st_b))
         self.last_stats = (st_f.as_dict(), st_b.as_dict()) if self.frames > 1 else None
         n = int(cnt[0])
         xy = np.empty((n, 2), dtype=np.float32)
         status = np.empty(n, dtype=np.uint8)
         start = np.empty(n, dtype=np.int32)
         if n:
-            ctx.check(ctx.lib.of_tracks_read(ctx.handle, 0, n, nat.ptr(xy), nat.u8ptr(status), _i32ptr(start)))
+            self._call("read", 0, n, nat.ptr(xy), nat.u8ptr(status), nat.i32ptr(start))
         return TrackSnapshot(xy, status, start, int(cnt[1]), int(cnt[2]),
                              nat.interleaved(out_f) if flows else None, nat.interleaved(out_b) if flows else None,
                              occ_f, occ_b)
-
-    def close(self):
-        if self._ctx is not None:
-            ctx, self._ctx = self._ctx, None
-            if ctx.handle:
-                ctx.check(ctx.lib.of_tracks_close(ctx.handle))
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class Trajectories:
@@ -276,9 +221,7 @@ def track_points(frames, method='classic+nl-fast', params=None, step=8, max_trac
                  alpha2=0.5, beta1=0.01, beta2=0.002):
     """Track points through `frames` (a sequence of at least one (H, W) or
     (H, W, 3) frame of one shape) with a PointTracker; returns Trajectories."""
-    frames = [np.asarray(f) for f in frames]
-    if not frames or any(f.shape != frames[0].shape for f in frames):
-        raise ValueError("frames must be a non-empty sequence of frames of one shape")
+    frames = _clip(frames)
     with PointTracker(frames[0].shape, method, params, step, max_tracks, min_eig, alpha1, alpha2, beta1,
                       beta2) as tr:
         snaps = [tr.push(f) for f in frames]

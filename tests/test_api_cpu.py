@@ -117,6 +117,14 @@ def test_params_flattening():
     o.spatial_filters = [np.ones((1, 6))]  # beyond 5 x 5 taps
     with pytest.raises(NotImplementedError):
         o.to_params()
+    # guide_mode is to_params()'s to set: callers do not assign it again
+    from optical_flow.methods.config import METHOD_NAMES
+    for name in METHOD_NAMES:
+        for color in (False, True):
+            o = load_of_method(name)
+            o.color_images = np.ones((1, 1, 3)) if color else None
+            assert o.to_params().guide_mode == int(o._METHOD == 'classic_nl' and o.color_images is not None), \
+                (name, color)
 
 
 # ---- penalties (reference tests/test_robust_functions.py) ------------------

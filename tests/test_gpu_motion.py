@@ -357,6 +357,37 @@ def test_lifecycle_and_device_bytes():
     assert lib.of_stab_close(h) == _abi.OF_EINVAL  # none of the refused opens left a session behind
 
 
+def test_destroying_a_context_closes_its_open_sessions():
+    """of_ctx_destroy frees the sessions still open on the context; the Python
+    objects' later close() is then a silent no-op, and a fresh context gives
+    the same outputs bitwise."""
+    import optical_flow
+    from optical_flow import _native
+    from test_gpu_fuse import clip_frames
+    H, W = 32, 40
+    frames = clip_frames(H, W, 1, 4, 8, 2.0)
+
+    def run():
+        ctx = _native.Context()
+        tr = optical_flow.PointTracker((H, W), step=4, min_eig=1.0, context=ctx)
+        dn = optical_flow.TemporalDenoiser((H, W), sigma=8.0, context=ctx)
+        st = optical_flow.Stabilizer((H, W), radius=1, context=ctx)
+        outs = []
+        for f in frames:
+            snap, d, s = tr.push(f), dn.push(f), st.push(f)
+            outs += [snap.xy, snap.status, snap.start]
+            outs += [r[1] for r in (d, s) if r is not None]
+        ctx.close()  # with the three still open
+        for session in (tr, dn, st):
+            session.close()
+        return outs
+
+    first, second = run(), run()
+    assert len(first) == len(second) == 3 * 4 + 2 * 3
+    for a, b in zip(first, second):
+        assert a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
+
+
 # ---- end to end ----------------------------------------------------------------
 def jitter_clip():
     """Nine 64 x 96 views of one seeded smooth texture whose content sits at
