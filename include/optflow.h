@@ -833,6 +833,100 @@ int of_stab_flush(of_ctx *ctx, float *out, uint8_t *out_valid, double *out_trans
                   int32_t *out_index);
 int of_stab_close(of_ctx *ctx);
 
+/*
+ * Layered motion segmentation.  of_fit_motion finds one motion, the dominant
+ * one; of_segment_motion splits a flow into up to K parametric motions of one
+ * model, a label per pixel and a class for what no motion explains
+ * (OF_LAYER_NONE): hypotheses from a grid of cells, consensus extraction of one
+ * layer after the other, joint assign-and-refit rounds, a mode filter on the
+ * labels.  No session.  Everything in double from the fp32 inputs, no fma
+ * contraction, in exactly the order written; coordinates, models, w0, the 13
+ * sums with their order, the solve with its rank-loss fallback and the matrix
+ * are those of "Global motion estimation" above.  H * W >= 2^31: OF_ENOTSUP.
+ *
+ * Per pixel: s, cx, cy, x, y and w0 as in the fit.  r2(th, p) is the fit's r2
+ * of pixel p against th, (th0 + th1*x) + th2*y and so on, with the pixel's own
+ * (u, v).  A pixel is usable when w0 > 0; total = the number of usable pixels.
+ * c2 = cutoff*cutoff.  "count reaches the support" is
+ * !((double)count < min_support*(double)total).  Counts are integers.
+ * A pass "on a set M" is a pass k >= 1 of the fit with the cutoff c2 (never
+ * updated) in which every pixel outside M counts as masked by `state`:
+ * w = w0*[p in M]*((1 - t)*(1 - t)), t = min(r2/c2, 1.0).
+ *
+ * 1. Hypotheses.  Pass 0 of the fit (th = 0, w = w0) gives the 13 values of
+ *    every 8 x 64 tile; nty, ntx are the tile counts, g = grid,
+ *    ch = ceil(nty/g), cw = ceil(ntx/g).  Cell (a, b), 0 <= a, b < g, owns tile
+ *    rows [a*ch, min((a+1)*ch, nty)) and tile columns [b*cw, min((b+1)*cw, ntx));
+ *    an empty cell does not exist.  Each of a cell's 13 sums is its tiles'
+ *    values, in row-major order inside the cell, reduced by the group tree
+ *    (zero-padded to a multiple of 64, each group of 64 through the halving
+ *    tree, until one value is left).  Sw > 0: hypothesis a*g + b is the solve
+ *    of the model on those sums (a rank loss solves the translation);
+ *    otherwise the cell has no hypothesis.
+ * 2. Extraction, for l = 0 .. K-1, rem = the usable pixels not yet removed.
+ *    count_h = #{p in rem : r2(th_h, p) < c2} for every hypothesis h; h* has
+ *    the largest count, the lowest index on a tie.  No hypothesis, or count_h*
+ *    does not reach the support: stop.  th = th_h*; `passes` passes on rem,
+ *    each solved as in the fit; !(Sw > 0) ends the passes and keeps th.
+ *    inl = {p in rem : r2(th, p) < c2}.  #inl does not reach the support: the
+ *    layer is discarded and the extraction stops.  Otherwise th is layer l and
+ *    rem -= inl.  n = the layers extracted; they keep this order.
+ * 3. Joint rounds, `rounds` times: assign, then for every layer l one pass on
+ *    {usable p : label(p) = l}, solved when Sw > 0 (else th_l is kept).
+ *    Assign: a pixel whose u and v are finite, whatever its weight or state,
+ *    gets the layer with the smallest r2(th_l, p), the lowest l on a tie, if
+ *    that r2 < c2, and OF_LAYER_NONE otherwise; a pixel whose flow is not
+ *    finite gets OF_LAYER_NONE.  After the rounds the closing assignment
+ *    (labels_raw) and per layer one pass on its set that does not solve:
+ *    support = Sw, rms = sqrt(Sr/Sw) (NaN without support).  n = 0 is a valid
+ *    result: every label is OF_LAYER_NONE.
+ * 4. Mode filter, r = smooth > 0: the label of (i, j) becomes the value among
+ *    0 .. n-1, 255 that occurs most often in the in-frame part of the
+ *    (2r+1) x (2r+1) window of labels_raw around it, the smallest value on a
+ *    tie (so OF_LAYER_NONE loses ties).  One pass.  r = 0: labels = labels_raw.
+ *    pixels counts the returned plane.
+ * degenerate of a layer: 1 when the solve of its hypothesis or of one of its
+ * passes lost rank.
+ *
+ * Known limits.  A hypothesis cell is never finer than one 8 x 64 tile, so a
+ * layer without a nearly pure cell is found late or not at all: a 40 x 70
+ * frame split at 0.55 W lost the translation case, 67 x 131 and larger held at
+ * grid 8.  The smeared band along a motion boundary of an estimated flow
+ * comes out OF_LAYER_NONE, and on small frames as a thin extra layer once it
+ * exceeds min_support.
+ */
+#define OF_LAYER_NONE 255
+/* Any value out of range or not finite: OF_EINVAL, checked on the host before
+ * any launch. */
+typedef struct of_layers_opts {
+  int32_t model;        /* OF_MOTION_*, 0..2 */
+  int32_t max_layers;   /* K, 1..8 (4) */
+  int32_t grid;         /* g, hypothesis cells per axis, 1..16 (8) */
+  int32_t passes;       /* Tukey refits of an extracted layer, 0..16 (4) */
+  int32_t rounds;       /* joint assign-and-refit rounds, 0..16 (3) */
+  int32_t smooth;       /* radius of the label mode filter, 0..3 (2) */
+  double cutoff;        /* c, pixels, finite, > 0 (1.0) */
+  double min_support;   /* fraction of the usable pixels a layer must explain, (0, 1] (0.03) */
+} of_layers_opts;
+typedef struct of_motion_layer {
+  double theta[6];
+  double matrix[6];
+  double support;       /* Sw of the closing pass */
+  double rms;           /* sqrt(Sr/Sw) of the closing pass */
+  int64_t pixels;       /* pixels that carry this label in the returned plane */
+  int32_t degenerate;   /* 1: a solve of this layer lost rank */
+  int32_t pad_;
+} of_motion_layer;
+/*
+ *   uv, weight, state : as of_fit_motion
+ *   layers            : max_layers entries; the first *n_layers are written
+ *   labels            : H x W bytes, 0 .. n-1 or OF_LAYER_NONE
+ *   labels_raw        : H x W bytes, the labels before the mode filter, or NULL
+ */
+int of_segment_motion(of_ctx *ctx, const float *uv, int H, int W, const float *weight, const uint8_t *state,
+                      const of_layers_opts *opts, of_motion_layer *layers, int32_t *n_layers, uint8_t *labels,
+                      uint8_t *labels_raw);
+
 /* compute_flow_base() for one pyramid level with the given alpha (one call =
  * all warping iterations of the level; hs.py:109-142, ba.py:143-206,
  * classic_nl.py:200-277).  uv_in / out_uv planar 2 x H x W. */

@@ -21,6 +21,7 @@
 //   host_track.hip  point tracker: advance and seed steps, stage entries, the session
 //   host_fuse.hip   temporal denoising: flow composition, frame fusion, stage entries, the session
 //   host_motion.hip global motion: the robust parametric fit, the affine warp, path smoothing, the stabiliser session
+//   host_layers.hip layered motion segmentation: hypotheses, extraction, joint rounds, the stage entry
 //   batch.hip       lanes, of_pairs_run[_host], pair pool, slot copies, RCCL gather
 //   api.hip         context, options, profiling, single-pair and stage entries
 #include <hip/hip_runtime.h>
@@ -46,6 +47,7 @@
 #include "kernels_track.hip"
 #include "kernels_fuse.hip"
 #include "kernels_motion.hip"
+#include "kernels_layers.hip"
 #include "kernels_solve.hip"
 #include "kernels_gen.hip"
 
@@ -57,5 +59,6 @@
 #include "host_track.hip"
 #include "host_fuse.hip"
 #include "host_motion.hip"
+#include "host_layers.hip"
 #include "batch.hip"
 #include "api.hip"

@@ -34,45 +34,70 @@ void motion_matrix(const double *th, const MotionFrame &fr, double *M) {
   M[5] = th[3] - (th[4] * fr.cx + th[5] * fr.cy) / s;
 }
 
+// What the passes of a fit on an H x W flow share: the tile geometry, the
+// frame's coordinates and the two arena buffers of the group tree.
+struct MotionPasses {
+  int H, W, ntx, nty, nt;  // nt < 2^31 / 8
+  MotionFrame fr;
+  double *rec[2];
+  int stride[2];
+  unsigned tile_blocks() const { return (unsigned)((nt + MOT_WAVES - 1) / MOT_WAVES); }
+};
+MotionPasses motion_passes(of_ctx *c, int H, int W) {
+  MotionPasses p;
+  p.H = H;
+  p.W = W;
+  p.ntx = (W + MOT_TW - 1) / MOT_TW;
+  p.nty = (H + MOT_TH - 1) / MOT_TH;
+  p.nt = p.ntx * p.nty;
+  p.stride[0] = p.nt;
+  p.stride[1] = (p.nt + 63) / 64;
+  for (int k = 0; k < 2; ++k) p.rec[k] = (double *)c->arena.alloc(sizeof(double) * MOT_NS * p.stride[k]);
+  p.fr.s = 0.5 * (double)(H > W ? H : W);
+  p.fr.cx = 0.5 * (double)(W - 1);
+  p.fr.cy = 0.5 * (double)(H - 1);
+  return p;
+}
+// the tile records of one pass into p.rec[0]
+void motion_part(of_ctx *c, const MotionPasses &p, const F2 &f, const float *dw, const uint8_t *ds,
+                 const MotionState *ms, int pass, float *d_inl) {
+  launch(c, "motion_part", k_motion_part, dim3(p.tile_blocks()), dim3(MOT_WAVES * 64), 0, (const float2 *)f.p, p.H, p.W,
+         f.P, dw, ds, ms, pass, p.fr, p.ntx, p.nt, p.stride[0], p.rec[0], d_inl);
+}
+// One pass queued on the stream: the tile sums, the group tree down to <= 64
+// values, then the last level with the solve; th and c2 stay in ms.
+void motion_pass(of_ctx *c, const MotionPasses &p, const F2 &f, const float *dw, const uint8_t *ds, MotionState *ms,
+                 int pass, int model, double kappa2, double decay, double cmin2, float *d_inl) {
+  motion_part(c, p, f, dw, ds, ms, pass, d_inl);
+  int n = p.nt, src = 0;
+  while (n > 64) {  // the upper levels ping-pong between the two buffers
+    const int ng = (n + 63) / 64;
+    launch(c, "motion_group", k_motion_group, dim3((unsigned)((ng + MOT_WAVES - 1) / MOT_WAVES)), dim3(MOT_WAVES * 64),
+           0, (const double *)p.rec[src], n, p.stride[src], p.rec[src ^ 1], p.stride[src ^ 1], (const MotionState *)ms,
+           pass);
+    n = ng;
+    src ^= 1;
+  }
+  launch(c, "motion_final", k_motion_final, dim3(1), dim3(64), 0, (const double *)p.rec[src], n, p.stride[src], ms, pass,
+         model, kappa2, decay, cmin2);
+}
+
 // The fit of `o` on the device-resident flow f; dw (dense H x W weights) and
 // ds (dense H x W states) may be nullptr, d_inl (dense H x W) too.  Pass 0,
-// o.iters robust passes and the last pass are queued as one chain: per pass
-// the tile sums, the group tree down to <= 64 values, then the last level with
-// the solve, th and c2 staying on the device.  One small read-back and one
-// stream synchronisation at the end.
+// o.iters robust passes and the last pass are queued as one chain.  One small
+// read-back and one stream synchronisation at the end.
 void fit_motion_dev(of_ctx *c, const F2 &f, const float *dw, const uint8_t *ds, const of_motion_opts &o,
                     of_motion_fit *out, float *d_inl) {
-  const int H = f.H, W = f.W;
-  const int ntx = (W + MOT_TW - 1) / MOT_TW, nty = (H + MOT_TH - 1) / MOT_TH;
-  const int nt = ntx * nty;  // < 2^31 / 8
-  const int s0 = nt, s1 = (nt + 63) / 64;
-  double *rec[2] = {(double *)c->arena.alloc(sizeof(double) * MOT_NS * s0),
-                    (double *)c->arena.alloc(sizeof(double) * MOT_NS * s1)};
-  const int stride[2] = {s0, s1};
+  const MotionPasses p = motion_passes(c, f.H, f.W);
+  const MotionFrame &fr = p.fr;
   MotionState *ms = (MotionState *)c->arena.alloc(sizeof(MotionState));
-  MotionFrame fr;
-  fr.s = 0.5 * (double)(H > W ? H : W);
-  fr.cx = 0.5 * (double)(W - 1);
-  fr.cy = 0.5 * (double)(H - 1);
   const double kappa2 = o.kappa * o.kappa, cmin2 = o.c_min * o.c_min;
-  c->cur_px = (double)H * W;
+  c->cur_px = (double)f.H * f.W;
   launch(c, "motion_init", k_motion_init, dim3(1), dim3(64), 0, ms, cmin2);
   for (int k = 0; k <= o.iters + 1; ++k) {
     const int pass = k == 0 ? MOT_PASS_FIRST : (k <= o.iters ? MOT_PASS_ROBUST : MOT_PASS_LAST);
-    launch(c, "motion_part", k_motion_part, dim3((unsigned)((nt + MOT_WAVES - 1) / MOT_WAVES)), dim3(MOT_WAVES * 64), 0,
-           (const float2 *)f.p, H, W, f.P, dw, ds, (const MotionState *)ms, pass, fr, ntx, nt, s0, rec[0],
-           pass == MOT_PASS_LAST ? d_inl : (float *)nullptr);
-    int n = nt, src = 0;
-    while (n > 64) {  // the upper levels ping-pong between the two buffers
-      const int ng = (n + 63) / 64;
-      launch(c, "motion_group", k_motion_group, dim3((unsigned)((ng + MOT_WAVES - 1) / MOT_WAVES)),
-             dim3(MOT_WAVES * 64), 0, (const double *)rec[src], n, stride[src], rec[src ^ 1], stride[src ^ 1],
-             (const MotionState *)ms, pass);
-      n = ng;
-      src ^= 1;
-    }
-    launch(c, "motion_final", k_motion_final, dim3(1), dim3(64), 0, (const double *)rec[src], n, stride[src], ms, pass,
-           o.model, kappa2, o.decay, cmin2);
+    motion_pass(c, p, f, dw, ds, ms, pass, o.model, kappa2, o.decay, cmin2,
+                pass == MOT_PASS_LAST ? d_inl : (float *)nullptr);
   }
   MotionState h;
   HIPCHK(hipMemcpyAsync(&h, ms, sizeof(h), hipMemcpyDeviceToHost, c->stream));

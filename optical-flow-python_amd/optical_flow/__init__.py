@@ -10,7 +10,8 @@ from optical_flow.interface import (estimate_flow, estimate_flow_batch, PairStre
 from optical_flow.tracking import (advance_points, seed_points, PointTracker, track_points, Trajectories,
                                    TRACK_ALIVE, TRACK_OCCLUDED, TRACK_LEFT_FRAME, TRACK_MOTION_BOUNDARY)
 from optical_flow.temporal import compose_flows, fuse_frames, TemporalDenoiser, denoise_frames
-from optical_flow.motion import fit_motion, warp_affine, Stabilizer, stabilize_frames, MotionFit
+from optical_flow.motion import (fit_motion, warp_affine, Stabilizer, stabilize_frames, MotionFit, segment_motion,
+                                 MotionLayers, MotionLayer, LAYER_NONE)
 from optical_flow.utils.warping import warp_image
 from optical_flow.utils.occlusion import forward_backward_check, FB_CONSISTENT, FB_OCCLUDED, FB_OUT_OF_FRAME
 from optical_flow.io.flo_io import read_flo, write_flo
@@ -25,4 +26,5 @@ __all__ = ['estimate_flow', 'estimate_flow_batch', 'PairStream', 'read_flo', 'wr
            'INTERP_FRAME1_ONLY', 'INTERP_FRAME2_ONLY', 'INTERP_NEITHER', 'INTERP_FILLED', 'advance_points',
            'seed_points', 'PointTracker', 'track_points', 'Trajectories', 'TRACK_ALIVE', 'TRACK_OCCLUDED',
            'TRACK_LEFT_FRAME', 'TRACK_MOTION_BOUNDARY', 'compose_flows', 'fuse_frames', 'TemporalDenoiser',
-           'denoise_frames', 'fit_motion', 'warp_affine', 'Stabilizer', 'stabilize_frames', 'MotionFit']
+           'denoise_frames', 'fit_motion', 'warp_affine', 'Stabilizer', 'stabilize_frames', 'MotionFit',
+           'segment_motion', 'MotionLayers', 'MotionLayer', 'LAYER_NONE']

@@ -166,6 +166,21 @@ class OfStabOpts(C.Structure):
                 ("alpha1", C.c_double), ("alpha2", C.c_double)]
 
 
+# layered motion segmentation (include/optflow.h, "Layered motion segmentation")
+OF_LAYER_NONE = 255
+LAYERS_MAX, LAYERS_MAX_GRID, LAYERS_MAX_PASSES, LAYERS_MAX_ROUNDS, LAYERS_MAX_SMOOTH = 8, 16, 16, 16, 3
+
+
+class OfLayersOpts(C.Structure):
+    _fields_ = [("model", C.c_int32), ("max_layers", C.c_int32), ("grid", C.c_int32), ("passes", C.c_int32),
+                ("rounds", C.c_int32), ("smooth", C.c_int32), ("cutoff", C.c_double), ("min_support", C.c_double)]
+
+
+class OfMotionLayer(C.Structure):
+    _fields_ = [("theta", C.c_double * 6), ("matrix", C.c_double * 6), ("support", C.c_double), ("rms", C.c_double),
+                ("pixels", C.c_int64), ("degenerate", C.c_int32), ("pad_", C.c_int32)]
+
+
 def penalty(kind, p0=1.0, p1=0.0):
     return OfPenalty(PENALTY[kind], 0, float(p0), float(p1))
 

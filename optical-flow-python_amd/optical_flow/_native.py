@@ -11,7 +11,8 @@ import threading
 import numpy as np
 
 from optical_flow._abi import (OfParams, OfStats, OfCgGeometry, OfSolveRecord, OfProgressFn, OfTrackOpts, OfFuseOpts,
-                               OfMotionOpts, OfMotionFit, OfStabOpts, OF_ABI_VERSION, OF_EINVAL, OF_ENOTSUP)
+                               OfMotionOpts, OfMotionFit, OfStabOpts, OfLayersOpts, OfMotionLayer, OF_ABI_VERSION,
+                               OF_EINVAL, OF_ENOTSUP)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("OPTFLOW_LIB", os.path.join(_HERE, "_lib", "liboptflow.so"))
@@ -84,6 +85,8 @@ _SIGS = {
     "of_stab_push": ([_vp, _fp, _fp, _u8p, _dp, _dp, _i32p, _i32p], C.c_int),
     "of_stab_flush": ([_vp, _fp, _u8p, _dp, _i32p, _i32p], C.c_int),
     "of_stab_close": ([_vp], C.c_int),
+    "of_segment_motion": ([_vp, _fp, C.c_int, C.c_int, _fp, _u8p, C.POINTER(OfLayersOpts), C.POINTER(OfMotionLayer),
+                           _i32p, _u8p, _u8p], C.c_int),
     "of_compute_flow_base": ([_vp, C.POINTER(OfParams), _fp, C.c_int, C.c_int, C.c_int, _fp, C.c_int,
                               C.c_double, _fp, _fp], C.c_int),
     "of_alt_ba_flow_base": ([_vp, C.POINTER(OfParams), _fp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, _fp,

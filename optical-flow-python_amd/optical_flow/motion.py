@@ -2,7 +2,9 @@
 dominant motion of a flow field is fitted on the GPU as a translation, a
 similarity or an affine map by iteratively reweighted least squares with a
 decreasing Tukey cutoff; a stabiliser smooths the chain of those motions over
-a clip and warps every frame onto the smoothed camera path.
+a clip and warps every frame onto the smoothed camera path; segment_motion
+splits a flow into several such motions with a label per pixel
+("Layered motion segmentation" there).
 include/optflow.h ("Global motion estimation and video stabilisation") states
 the arithmetic; in a session the frames and flows stay on the GPU
 (of_stab_*), only the six numbers of each motion visit the host.
@@ -97,6 +99,61 @@ def warp_affine(im, matrix, return_valid=False):
                                      nat.dptr(A), nat.ptr(out), nat.u8ptr(valid)))
     out = out.astype(np.float64)
     return (out, valid) if return_valid else out
+
+
+LAYER_NONE = _abi.OF_LAYER_NONE
+
+MotionLayer = namedtuple("MotionLayer", "theta matrix support rms pixels degenerate")
+MotionLayer.__doc__ = """One layer of segment_motion: `theta`, `matrix` (2, 3), `support` and `rms` as
+in MotionFit, from the closing pass over the layer's pixels; `pixels` the
+pixels that carry the layer's label; `degenerate` 1 when a solve of the layer
+lost rank and solved the translation."""
+
+MotionLayers = namedtuple("MotionLayers", "labels layers n labels_raw")
+MotionLayers.__doc__ = """Result of segment_motion: `labels` (H, W) uint8, the index into `layers` or
+LAYER_NONE (255) where no layer explains the pixel; `layers` the `n`
+MotionLayer fits in extraction order; `labels_raw` the labels before the mode
+filter, or None."""
+
+
+def segment_motion(flow, model='affine', max_layers=4, grid=8, passes=4, rounds=3, smooth=2, cutoff=1.0,
+                   min_support=0.03, weight=None, state=None, return_raw=False):
+    """`flow` (H, W, 2) split into up to `max_layers` motions of `model` as a
+    MotionLayers (of_segment_motion).  Every cell of a `grid` x `grid`
+    partition of the frame proposes the least-squares motion of its own
+    pixels; the proposal that explains most of the pixels not yet claimed to
+    within `cutoff` pixels is refitted on them by `passes` Tukey passes and
+    claims its inliers, until a layer would explain less than `min_support` of
+    the usable pixels.  `rounds` rounds of assigning every pixel to its best
+    layer and refitting follow, and a mode filter of radius `smooth` cleans
+    the labels up.  `weight` and `state` as in fit_motion: they decide what
+    enters the fits; every pixel with a finite flow gets a label."""
+    flow = _flow("flow", flow)
+    H, W = flow.shape[:2]
+    _frame_size(H, W)
+    if not isinstance(model, str) or model not in _abi.MOTION_MODEL:
+        raise ValueError(f"model must be one of {sorted(_abi.MOTION_MODEL)}, got {model!r}")
+    min_support = _number("min_support", min_support, True)
+    if min_support > 1.0:
+        raise ValueError(f"min_support must be in (0, 1], got {min_support!r}")
+    opts = _abi.OfLayersOpts(_abi.MOTION_MODEL[model], _int_in("max_layers", max_layers, 1, _abi.LAYERS_MAX),
+                             _int_in("grid", grid, 1, _abi.LAYERS_MAX_GRID),
+                             _int_in("passes", passes, 0, _abi.LAYERS_MAX_PASSES),
+                             _int_in("rounds", rounds, 0, _abi.LAYERS_MAX_ROUNDS),
+                             _int_in("smooth", smooth, 0, _abi.LAYERS_MAX_SMOOTH), _number("cutoff", cutoff, True),
+                             min_support)
+    w = nat.data_weight(weight, H, W)
+    st = _state("state", state, H, W)
+    fits = (_abi.OfMotionLayer * opts.max_layers)()
+    n = C.c_int32(0)
+    labels = np.empty((H, W), dtype=np.uint8)
+    raw = np.empty((H, W), dtype=np.uint8) if return_raw else None
+    ctx = nat.context()
+    ctx.check(ctx.lib.of_segment_motion(ctx.handle, nat.ptr(_planar32(flow)), H, W, nat.ptr(w), nat.u8ptr(st),
+                                        C.byref(opts), fits, C.byref(n), nat.u8ptr(labels), nat.u8ptr(raw)))
+    layers = [MotionLayer(np.array(f.theta, dtype=np.float64), np.array(f.matrix, dtype=np.float64).reshape(2, 3),
+                          f.support, f.rms, int(f.pixels), f.degenerate) for f in fits[:n.value]]
+    return MotionLayers(labels, layers, n.value, raw)
 
 
 class Stabilizer(DelayedSession):
