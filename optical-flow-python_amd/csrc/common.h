@@ -168,6 +168,17 @@ __device__ __forceinline__ double wave_sum(double v) {
   return v;
 }
 
+// ---- wave shifts ------------------------------------------------------------
+// lane l <- lane l-1 (wave_shr:1) and lane l <- lane l+1 (wave_shl:1) across
+// the whole wave as one DPP move (row_shr / row_shl would stop at the 16-lane
+// rows; no ds_bpermute); a lane without a source reads 0 (bound_ctrl)
+__device__ __forceinline__ float wave_from_prev(float v) {
+  return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x138, 0xf, 0xf, true));
+}
+__device__ __forceinline__ float wave_from_next(float v) {
+  return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x130, 0xf, 0xf, true));
+}
+
 // Sum NV doubles over the block (256 threads max); result valid in thread 0.
 template <int NV>
 __device__ __forceinline__ void block_sum(double (&v)[NV], double *lds /* NV*16 */) {

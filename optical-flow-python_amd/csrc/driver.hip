@@ -11,6 +11,20 @@
 // 80-byte read per chunk of iterations, double-buffered so the GPU always
 // has the next chunk queued) and Horn-Schunck's ||x|| < 1e-3 early exit.
 //
+// Kernel files, one family each, in dependency order like the host parts:
+//   kernels_img.hip    colour, filters, resampling, pyramids, ROF
+//   kernels_flow.hip   warp, derivatives, system assembly, occlusion, medians, weighted median
+//   kernels_track.hip  point tracker: advance and seed steps
+//   kernels_fuse.hip   temporal denoising: flow composition, frame fusion
+//   kernels_motion.hip global motion: the passes of the robust parametric fit, the affine warp
+//   kernels_layers.hip layered motion segmentation (uses the fit's passes)
+//   kernels_solve.hip  what the solvers share (partials, fixed-order sums, residual), norm and residual diagnostics
+//   kernels_cg.hip     the fed CG: prologue, Jacobi iteration k_cg, check, residual replacement, finalize
+//   kernels_cgs.hip    the 'backslash' surrogate iteration k_cgs
+//   kernels_cg_wg.hip  a whole CG solve in one workgroup: k_cg_small, k_cg_reg
+//   kernels_sor.hip    lexicographic SOR: per-sweep, pipelined and one-workgroup forms
+//   kernels_gen.hip    CG on a general filter-bank operator (gen_*)
+//
 // Host parts, one concern each, in dependency order (a part uses only the
 // parts above it, so none needs a forward declaration of a later one):
 //   host_core.h     errors, arena, context, session base, profiling, launch(), shared checks, API_* macros
@@ -49,6 +63,10 @@
 #include "kernels_motion.hip"
 #include "kernels_layers.hip"
 #include "kernels_solve.hip"
+#include "kernels_cg.hip"
+#include "kernels_cgs.hip"
+#include "kernels_cg_wg.hip"
+#include "kernels_sor.hip"
 #include "kernels_gen.hip"
 
 #include "host_core.h"

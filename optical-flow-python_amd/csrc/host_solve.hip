@@ -1,4 +1,5 @@
 // host_solve.hip — host side of the linear solvers (kernels_solve.hip,
+// kernels_cg.hip, kernels_cgs.hip, kernels_cg_wg.hip, kernels_sor.hip,
 // kernels_gen.hip): the feed loops, the launch geometry, the CG and SOR
 // dispatchers, the solve log, the deferred solve statistics and the
 // general-filter (gen_*) solvers.
@@ -137,7 +138,7 @@ void note_solve(of_ctx *c, of_stats *st, const SolveResult &r) {
   else note_solve_now(st, r);
 }
 
-// Coefficients c_i of the degree-m polynomial preconditioner of k_cgp,
+// Coefficients c_i of the degree-m polynomial preconditioner of k_cgs,
 // M^-1 = sum_i c_i B^i D^-1 with B = I - X, X = D^-1 A: the Chebyshev
 // residual polynomial 1 - X p(X) = T_{m+1}((b + a - 2X) / (b - a)) /
 // T_{m+1}((b + a) / (b - a)), re-expanded in powers of B.
@@ -172,7 +173,7 @@ void cheb_poly(int m, double a, double b, double *cB) {
 }
 
 // Chebyshev interval [CG_CHEB_A, 2] of the block-Jacobi-scaled spectrum
-// D^-1 A of the 'backslash' preconditioner (kernels_solve.hip, k_cgs).  The
+// D^-1 A of the 'backslash' preconditioner (kernels_cgs.hip, k_cgs).  The
 // lower end trades iterations for parity: 0.06 saves 4 % of the iterations
 // but moves the 48x64 smoke pair's mean |uv - oracle| from 6.7e-4 to 6.1e-3
 // (knob sweep).
@@ -380,7 +381,7 @@ SolveResult solve_cg_small(of_ctx *c, const CgSetup &s, const Img &coef, const F
     launch(c, "pcg_small", s.block ? k_cg_reg<CG_DEG, true> : k_cg_reg<0, false>, dim3(1), dim3(64, CGR_T / 64), 0,
            a);
   else
-    launch(c, "pcg_small", s.block ? k_cg_small<CG_DEG, true> : k_cg_small<0, false>, dim3(1), dim3(CGS_BX, CGS_BY),
+    launch(c, "pcg_small", s.block ? k_cg_small<CG_DEG, true> : k_cg_small<0, false>, dim3(1), dim3(CGW_BX, CGW_BY),
            0, a);
   return cg_queued(c, s, coef, b, x, nullptr);
 }
@@ -440,8 +441,8 @@ SolveResult solve_cg(of_ctx *c, const CgSetup &s, const Img &coef, const F2 &b, 
     const bool odd = W & 1;
     auto kern = split ? (k == 0 ? (odd ? k_cgs<true, true> : k_cgs<true, false>)
                                 : (odd ? k_cgs<false, true> : k_cgs<false, false>))
-                      : (k == 0 ? (odd ? k_cg<true, false, true> : k_cg<true, false, false>)
-                                : (odd ? k_cg<false, false, true> : k_cg<false, false, false>));
+                      : (k == 0 ? (odd ? k_cg<true, true> : k_cg<true, false>)
+                                : (odd ? k_cg<false, true> : k_cg<false, false>));
     launch(c, "pcg_iter", kern, grid, blk, 0, args_k(k), k, R, nbands);
   });
   // the convergence test of the last enqueued iterate when the solve ran
@@ -452,7 +453,7 @@ SolveResult solve_cg(of_ctx *c, const CgSetup &s, const Img &coef, const F2 &b, 
 
 // ---- the SOR arms -------------------------------------------------------------
 // lexicographic SOR (base.py:138-172): 64-row strips of the u half then of
-// the v half (kernels_solve.hip); k_sor_wg and k_sor_pipe run many sweeps in
+// the v half (kernels_sor.hip); k_sor_wg and k_sor_pipe run many sweeps in
 // flight in one persistent launch, k_sor_lex one launch per sweep
 // (of_set_option OF_OPT_SOR_PIPELINE 0; the same iterate bitwise)
 SolveResult sor_result(const PcgState &st) {

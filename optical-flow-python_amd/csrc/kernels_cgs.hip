@@ -1,0 +1,593 @@
+// kernels_cgs.hip — k_cgs, the fed CG's iteration for the 'backslash'
+// surrogate: the polynomial preconditioner and the strip / halo geometry
+// (first comment), the LDS-ring records and their helpers (CgRec, CgRaw,
+// cgr_*), the CGS_* knobs with their measurement notes, and the kernel.
+// Expects kernels_solve.hip and kernels_cg.hip before it: PcgArgs, the cg_*
+// raw-buffer and packed helpers, cg_inv<true>, cg_prologue, write_partials.
+// Invariants as for k_cg: one launch per iteration with the launch-boundary
+// reduce, the same grid at every launch of a solve, out-of-image lanes load 0
+// and store nowhere.  CGS_ / cgs_ names belong to this kernel alone (the host
+// geometry knobs CGS_*_BLOCKS included); the one-workgroup CG is CGW_ / cgw_.
+#include "kernels.h"
+
+// ---------------------------------------------------------------------------
+// The 'backslash' surrogate iteration (k_cgs below): the fused, q-free CG
+// iteration with a degree-CG_DEG (5) polynomial preconditioner in the 2x2
+// block-Jacobi splitting A = D - N, B = D^-1 N:
+//   M^-1 = (c0 + c1 B + ... + c5 B^5) D^-1,
+// the Chebyshev polynomial that minimises max |1 - X p(X)| for the spectrum
+// of X = D^-1 A = I - B on [a, 2] (a = 0.04, 0.02 for the robust GNC stages;
+// host: cheb_poly; 2 bounds the spectrum because D + N is positive
+// semidefinite).  p > 0 there, so M is SPD.  (Round 1 used degree 3: 0.54x
+// the iterations of a first-order Neumann preconditioner, 0.27x of block
+// Jacobi; degree 5 takes 0.69x the iterations of degree 3.)
+//
+// z = M^-1 r by Horner, one neighbour exchange per stage:
+//   y = D^-1 r,  g4 = c4 y + c5 D^-1 N y,  g3 = c3 y + D^-1 N g4, ...,
+//   z = c0 y + D^-1 N g1   (and r.z = c0 r.y + y.N g1).
+// The rho recurrence needs q.M^-1 q = sum_i c_i T_i with y_q = D^-1 q,
+// v1 = D^-1 N y_q, v2 = D^-1 N v1:  T0 = y_q.q, T1 = y_q.N y_q, T2 = v1.N y_q,
+// T3 = v1.N v1, T4 = v2.N v1, T5 = v2.N v2 (each edge counted once, by its
+// right / lower pixel).
+// Seven stencil stages deep, so a strip carries four halo lanes per side
+// towards a neighbouring strip: strip t holds columns [112 t, 112 t + 128)
+// (lane l: columns 112 t + 2 l and + 1) and owns lanes 4..59 (PCG_SWP = 112
+// output columns).  The halo only recomputes the neighbour's pixels, so the
+// side of a strip that has no neighbour needs none: the first strip also
+// owns lanes 0..3 and the last strip lanes 60..63, i.e. 120 + 112 (n - 2) +
+// 120 columns over n strips (17 at 1920, not 18) and all 128 when one strip
+// covers the level.  Those lanes are exact as they stand: wave_from_prev /
+// wave_from_next are wave_shr:1 / wave_shl:1 DPP moves with bound_ctrl, so
+// lane 0 reads 0 as its left value and left weight (cgr_nsum's L and wl, T5's
+// h0) and lane 63 reads 0 as its right value (Rt), which is the operator at
+// the image's first and last column; columns >= W load 0 through CG_OOB, are
+// stored nowhere and count in no dot product (ok0 / ok1 in soff8, dm0, dm1
+// and the mask on p), and the ODD instances zero the pixel at column W.
+// Arithmetic is on (u, v)
+// pairs of one pixel (packed fp32: v_pk_fma_f32).  Each row's coefficients
+// are staged once into an LDS ring of records (per pixel the (u, v) weight
+// pairs of the edges right and below and D^-1 as (ia, ic), (ic, id)) that
+// every stage reads; D itself is re-formed from D^-1 where a stage needs it.
+
+// CGS_HALO: halo lanes per side of a k_cgs strip (2 px each).  Everything a launch
+// stores (r, p, x) and the dots p.q, q.z, r.z, r.r are exact with 4 (z
+// reaches 6 px out); only the T terms of q.M^-1 q at the strip's first and
+// last output columns reach 9-10 px (T5 uses v2 of the left neighbour), so
+// they see the DPP's zero beyond lane 0.  That moves only the rho
+// recurrence's beta: 5 halo lanes (108 output columns) give the same 479 CG
+// iterations per 1080p pair and the same pairs/s (profiles/r3ae_*), so 4.
+#ifndef CGS_HALO
+#define CGS_HALO 4
+#endif
+#define PCG_SWP (128 - 4 * CGS_HALO)
+#define CG_ROW_OOB 0x40000000u
+
+struct CgRec {  // one LDS-ring row: pixel e of the lane, (u, v) pairs
+  cg_f2 wx[2], wy[2];  // weights of the edges right of / below the pixel
+  cg_f2 ma[2], mb[2];  // D^-1 columns: (ia, ic), (ic, id)
+};
+struct CgRaw {  // staged global loads of one coefficient row (plane order)
+  cg_f2 wxu, wyu, wxv, wyv, a, c, d;
+};
+
+__device__ __forceinline__ cg_f2 cg_lo(cg_f4 v) { return cg_f2{v.x, v.y}; }
+__device__ __forceinline__ cg_f2 cg_hi(cg_f4 v) { return cg_f2{v.z, v.w}; }
+__device__ __forceinline__ cg_f4 cg_cat(cg_f2 a, cg_f2 b) { return cg_f4{a.x, a.y, b.x, b.y}; }
+__device__ __forceinline__ cg_f2 cg_left2(cg_f2 v) { return cg_f2{wave_from_prev(v.x), wave_from_prev(v.y)}; }
+__device__ __forceinline__ cg_f2 cg_right2(cg_f2 v) { return cg_f2{wave_from_next(v.x), wave_from_next(v.y)}; }
+
+// N f of the middle row; wu = vertical weight pairs of the row above
+__device__ __forceinline__ cg_f4 cgr_nsum(cg_f4 up, cg_f4 mid, cg_f4 dn, const CgRec &c, const cg_f2 (&wu)[2]) {
+  const cg_f2 m0 = cg_lo(mid), m1 = cg_hi(mid);
+  const cg_f2 L = cg_left2(m1), Rt = cg_right2(m0), wl = cg_left2(c.wx[1]);
+  const cg_f2 s0 = wl * L + c.wx[0] * m1 + wu[0] * cg_lo(up) + c.wy[0] * cg_lo(dn);
+  const cg_f2 s1 = c.wx[0] * m0 + c.wx[1] * Rt + wu[1] * cg_hi(up) + c.wy[1] * cg_hi(dn);
+  return cg_cat(s0, s1);
+}
+__device__ __forceinline__ cg_f4 cgr_minv(const CgRec &m, cg_f4 r) {
+  const cg_f2 z0 = m.ma[0] * r.x + m.mb[0] * r.y;
+  const cg_f2 z1 = m.ma[1] * r.z + m.mb[1] * r.w;
+  return cg_cat(z0, z1);
+}
+// D f with D re-formed from the stored D^-1 (its 2x2 inverse; scalar-Jacobi
+// rows, ic = 0, give diag(1/ia, 1/id); all-zero records give D = 0)
+__device__ __forceinline__ cg_f4 cgr_diag(const CgRec &m, cg_f4 f) {
+  cg_f2 o[2];
+#pragma unroll
+  for (int e = 0; e < 2; ++e) {
+    const float ia = m.ma[e].x, ic = m.ma[e].y, id = m.mb[e].y;
+    const float det = ia * id - ic * ic;
+    const float inv = det != 0.f ? __builtin_amdgcn_rcpf(det) : 0.f;
+    const cg_f2 da = cg_f2{id, -ic} * inv, db = cg_f2{-ic, ia} * inv;
+    const float fu = e ? f.z : f.x, fv = e ? f.w : f.y;
+    o[e] = da * fu + db * fv;
+  }
+  return cg_cat(o[0], o[1]);
+}
+// D f from the raw coefficient row (wave 0 still holds it): no inverse
+__device__ __forceinline__ cg_f4 cgr_diag_raw(const CgRaw &c, cg_f4 f) {
+  const cg_f2 u = cg_f2{f.x, f.z}, v = cg_f2{f.y, f.w};
+  const cg_f2 du = c.a * u + c.c * v, dv = c.c * u + c.d * v;
+  return cg_f4{du.x, dv.x, du.y, dv.y};
+}
+
+// ---------------------------------------------------------------------------
+// k_cgs: the degree-CG_DEG (5) iteration above with its pipeline stages
+// split over the 4 waves of a block, which all work on ONE band:
+//   wave 0: loads, coefficient records -> LDS ring, A) r, y of row n-1
+//   wave 1: Horner B) g4 (row n-3), g3 (n-4), g2 (n-5), g1 (n-6)
+//   wave 2: D) z, p, x of row n-8, E) q, y_q of row n-9
+//   wave 3: F) v1 and T1, T2 (row n-11), v2 and T3..T5 (row n-12)
+// with one block barrier per row step; rows cross waves through small LDS
+// rings (y, g1, y_q; records in a 14-row ring), a wave's own rows stay in
+// registers.  (The round-1 form of this iteration, since removed, gave each
+// wave its own band and the whole pipeline: its record ring allowed one wave
+// per SIMD and 1.6x the rows read.)  Here 74 KB of LDS per block allow 2 blocks per CU (R = 39 at
+// 1080p) and a step costs only the heaviest wave's share.  Stage lags follow
+// from one barrier per step: a stage reads rows of another wave produced at
+// earlier steps; the band is walked for n in [r0 - 8, r1 + 11] so that every
+// row a required stage reads was produced.
+// Rejected variants of this kernel (record split over waves 0 / 3, register
+// record rings, raw-D stage E, pair-block splitting, trimmed drain loads)
+// are recorded with their measurements in DESIGN.md §3; the commits that
+// measured them hold their source.
+#define CGS_NREC 14
+// CGS_W0REG (default 1): wave 0 keeps the records of rows n-1, n-2 it
+// formed in registers instead of reading them back from the LDS ring (4
+// ds_read_b128 + 2 ds_read_b64 and their wait per row step of the
+// pace-setting wave; 184 -> 202 VGPRs, the same 2 waves / SIMD).  Round-5
+// A/B, 2 reps, the same flow bitwise (profiles/r5s_cgs_ab.log): isolated
+// 200-iteration 1080p solve 3.87 / 3.87 vs 3.96 / 3.92 ms, timed bench 47.95 /
+// 47.94 vs 47.94 / 47.87 pairs/s.  Masking the out-of-band rows instead of
+// branching over them (one basic block per row step) was 5 % slower as timed.
+// Also measured and removed (round 5, profiles/r5u_cgs_w3rec_ab.log): the
+// coefficient loads and records moved from wave 0 to wave 3 (one row ahead,
+// a 15-row ring): wave 0 101 -> 89 K working cycles per launch but wave 3
+// 56 -> 92 K, a 200-iteration 1080p solve 4.19 vs 3.90 ms, 45.0 vs 47.8
+// pairs/s, the same flow bitwise.
+#ifndef CGS_W0REG
+#define CGS_W0REG 1
+#endif
+// Waves 1 and 3 run at issue priority 1 (0 otherwise), above the
+// other lanes' kernels that share their SIMDs in the timed geometry: 45.65 /
+// 45.78 / 45.87 vs 45.34 / 45.45 / 45.57 pairs/s, 3 reps each
+// (profiles/r4k_prio_ab.log); the same arithmetic
+
+// Load distance in row steps (each step ends at a block barrier, so a load
+// issued at step n is waited for at step n + distance): wave 0's coefficient,
+// p_old and r_in rows (CGS_PF), wave 2's p_old and x rows (CGS_PF2).  Ring
+// sizes are powers of two dividing the 8-step unroll.
+#ifndef CGS_PF
+#define CGS_PF 2
+#endif
+// The distance holds only while every row step issues the same memory
+// operations: the compiler sizes each s_waitcnt vmcnt for the fewest
+// operations any path can have put behind the awaited load.  With wave 2's x
+// load and stores under branches it waited with vmcnt(1), i.e. for the p_old
+// load of the same step (distance 0, whatever CGS_PF2 said: the round-2
+// sweep of 2..4 was flat for that reason).  Unconditional (load_x, so8) the
+// wait is vmcnt(5) at distance 1, vmcnt(9) at 2.  Timed bench, 5 alternating
+// runs each on one box, the same flow bitwise: conditional 51.01 +- 0.04,
+// then CGS_PF2 1 / 2 / 3: 52.55 +- 0.14 / 53.02 +- 0.08 / 52.78 +- 0.04
+// pairs/s (profiles/r7_cgs_waits/).
+#ifndef CGS_PF2
+#define CGS_PF2 2
+#endif
+#define CGS_POW2(n) ((n) <= 1 ? 1 : (n) <= 2 ? 2 : (n) <= 4 ? 4 : 8)
+#define CGS_SGN CGS_POW2(CGS_PF + 2)
+#define CGS_RIN CGS_POW2(CGS_PF + 1)
+#define CGS_W2N CGS_POW2(CGS_PF2 + 1)
+static_assert(CGS_PF >= 1 && CGS_PF + 3 <= 8 && CGS_PF2 >= 1 && CGS_PF2 + 1 <= 8, "k_cgs load distances");
+
+// CGS_PHASE_TIMING (tools/micro builds only): per role, the cycles a wave
+// spends working and waiting at the row-step barriers
+#ifdef CGS_PHASE_TIMING
+__device__ unsigned long long g_cgs_t[4][3];  // [role] {work, wait, waves}
+#define CGS_T0 unsigned long long cgs_wait = 0, cgs_t_start = clock64();
+#define CGS_BAR_BEGIN const unsigned long long cgs_b0 = clock64();
+#define CGS_BAR_END cgs_wait += clock64() - cgs_b0;
+#define CGS_T1                                                           \
+  if (lane == 0) {                                                       \
+    const unsigned long long tot = clock64() - cgs_t_start;              \
+    atomicAdd(&g_cgs_t[wid][0], tot - cgs_wait);                         \
+    atomicAdd(&g_cgs_t[wid][1], cgs_wait);                               \
+    atomicAdd(&g_cgs_t[wid][2], 1ull);                                   \
+  }
+#else
+#define CGS_T0
+#define CGS_BAR_BEGIN
+#define CGS_BAR_END
+#define CGS_T1
+#endif
+
+template <bool FIRST, bool ODD>
+__global__ __launch_bounds__(256) void k_cgs(PcgArgs g, int k, int R, int nbands) {
+  __shared__ double lds[64];
+  __shared__ float4 ring[CGS_NREC][4][64];  // [row slot][record quarter][lane]
+  __shared__ float4 s_y[8][64], s_g1[4][64], s_yq[4][64];
+  const int H = g.H, W = g.W;
+  const unsigned rowb4 = (unsigned)g.P * 4u, rowb8 = (unsigned)g.P * 8u;
+  const size_t vbytes = (size_t)H * g.P * 8;
+  const __amdgpu_buffer_rsrc_t rc = cg_rsrc(g.coef, g.ps * 7 * 4);
+  const __amdgpu_buffer_rsrc_t rin = cg_rsrc(FIRST ? g.b : g.r_in, vbytes);
+  const __amdgpu_buffer_rsrc_t rpo = cg_rsrc(g.p_old, vbytes);
+  const __amdgpu_buffer_rsrc_t rx = cg_rsrc(g.x, vbytes);
+  const __amdgpu_buffer_rsrc_t rro = cg_rsrc(g.r_out, vbytes);
+  const __amdgpu_buffer_rsrc_t rpn = cg_rsrc(g.p_new, vbytes);
+  const unsigned ps4 = (unsigned)(g.ps * 4);
+  // XCD-aware tile order: blocks b, b + 8, b + 16 ... share an XCD's L2
+  // (MI355X_MICROARCH.md, workgroup dispatch), so give each XCD a contiguous
+  // run of row-major tiles; its neighbours' column halos are then read
+  // through the same L2 at about the same row step
+  const int nt = gridDim.x * gridDim.y, lin = blockIdx.x + blockIdx.y * gridDim.x;
+  const int xcd = lin & 7, tile = xcd * (nt >> 3) + min(xcd, nt & 7) + (lin >> 3);
+  const int lane = threadIdx.x, wid = __builtin_amdgcn_readfirstlane(threadIdx.y), band = tile / gridDim.x;
+  const int tid = lane + wid * 64;
+  // pipeline role of this wave (A/B, round 2: pairing the roles of two
+  // co-resident blocks differently on the SIMDs, role = wid ^ f(block), was
+  // no faster: 51.5-54 vs 52 us per 1080p launch)
+  const int role = wid;
+  // strip tx spans columns [PCG_SWP tx, PCG_SWP tx + 128): lanes 4..59 are
+  // output; the first strip's lanes 0..3 and the last strip's lanes 60..63
+  // have no neighbouring strip to recompute for, so they are output too
+  const int tx = tile - band * gridDim.x;
+  const int jc = tx * PCG_SWP + 2 * lane;
+  const bool ok0 = jc < W, ok1 = jc + 1 < W;
+  const bool out_lane = (lane >= CGS_HALO || tx == 0) && (lane < 64 - CGS_HALO || tx == (int)gridDim.x - 1);
+  const unsigned off4 = ok0 ? (unsigned)jc * 4u : CG_OOB, off8 = ok0 ? (unsigned)jc * 8u : CG_OOB;
+  const unsigned soff8 = ok0 && out_lane ? (unsigned)jc * 8u : CG_OOB;
+  const bool live = band < nbands;
+  // odd bands walk bottom to top, so each band meets its neighbours' halo
+  // rows at the same row step (both at the start or both at the end of the
+  // walk) and the second read of those rows is served by the XCD's L2.  The
+  // walk runs in virtual rows t (orig row H-1-t when flipped); the lower
+  // edge of virtual row t is the upper edge of its orig row, i.e. the wy
+  // stored at orig row H-2-t.
+  const bool flip = band & 1;
+  const int rb0 = band * R, rb1 = min(rb0 + R, H);
+  const int r0 = flip ? H - rb1 : rb0, r1 = flip ? H - rb0 : rb1;
+  const float c0 = g.poly[0], c1 = g.poly[1], c2 = g.poly[2], c3 = g.poly[3], c4 = g.poly[4], c5 = g.poly[5];
+  auto orow = [&](int t) { return (unsigned)(flip ? H - 1 - t : t); };
+  auto o4 = [&](int t) { return off4 + ((unsigned)t < (unsigned)H ? orow(t) * rowb4 : CG_ROW_OOB); };
+  auto o8 = [&](int t) { return off8 + ((unsigned)t < (unsigned)H ? orow(t) * rowb8 : CG_ROW_OOB); };
+  auto o4w = [&](int t) {
+    return flip ? off4 + ((unsigned)t < (unsigned)(H - 1) ? (unsigned)(H - 2 - t) * rowb4 : CG_ROW_OOB) : o4(t);
+  };
+  auto load_raw = [&](int t, CgRaw &c) {
+    const unsigned v = o4(t), vw = o4w(t);
+    c.wxu = cg_mask1<ODD>(cg_ld2(rc, v, 0), ok1);
+    c.wyu = cg_mask1<ODD>(cg_ld2(rc, vw, ps4), ok1);
+    c.wxv = cg_mask1<ODD>(cg_ld2(rc, v, 2 * ps4), ok1);
+    c.wyv = cg_mask1<ODD>(cg_ld2(rc, vw, 3 * ps4), ok1);
+    c.a = cg_mask1<ODD>(cg_ld2(rc, v, 4 * ps4), ok1);
+    c.c = cg_mask1<ODD>(cg_ld2(rc, v, 5 * ps4), ok1);
+    c.d = cg_mask1<ODD>(cg_ld2(rc, v, 6 * ps4), ok1);
+  };
+  // records are keyed by absolute row (rows >= r0 - 7 >= -7)
+  auto rslot = [](int t) { return (t + 2 * CGS_NREC) % CGS_NREC; };
+  auto put_rec = [&](int t, const CgRaw &c) {
+    CgCoef cc;
+    cc.a = c.a;
+    cc.c = c.c;
+    cc.d = c.d;
+    const CgInv mi = cg_inv<true>(cc);
+    float4 *q = &ring[rslot(t)][0][lane];
+    q[0] = make_float4(c.wxu.x, c.wxv.x, c.wyu.x, c.wyv.x);
+    q[64] = make_float4(c.wxu.y, c.wxv.y, c.wyu.y, c.wyv.y);
+    q[128] = make_float4(mi.ia.x, mi.ic.x, mi.ic.x, mi.id.x);
+    q[192] = make_float4(mi.ia.y, mi.ic.y, mi.ic.y, mi.id.y);
+    CgRec r;  // the record as get_rec reads it back
+    r.wx[0] = cg_f2{c.wxu.x, c.wxv.x};
+    r.wy[0] = cg_f2{c.wyu.x, c.wyv.x};
+    r.wx[1] = cg_f2{c.wxu.y, c.wxv.y};
+    r.wy[1] = cg_f2{c.wyu.y, c.wyv.y};
+    r.ma[0] = cg_f2{mi.ia.x, mi.ic.x};
+    r.mb[0] = cg_f2{mi.ic.x, mi.id.x};
+    r.ma[1] = cg_f2{mi.ia.y, mi.ic.y};
+    r.mb[1] = cg_f2{mi.ic.y, mi.id.y};
+    return r;
+  };
+  auto get_rec = [&](int t) {
+    const float4 *q = &ring[rslot(t)][0][lane];
+    const float4 a = q[0], b = q[64], c = q[128], d = q[192];
+    CgRec r;
+    r.wx[0] = cg_f2{a.x, a.y};
+    r.wy[0] = cg_f2{a.z, a.w};
+    r.wx[1] = cg_f2{b.x, b.y};
+    r.wy[1] = cg_f2{b.z, b.w};
+    r.ma[0] = cg_f2{c.x, c.y};
+    r.mb[0] = cg_f2{c.z, c.w};
+    r.ma[1] = cg_f2{d.x, d.y};
+    r.mb[1] = cg_f2{d.z, d.w};
+    return r;
+  };
+  auto get_wy = [&](int t, cg_f2 (&wu)[2]) {  // vertical weight pairs only
+    const float2 *q = reinterpret_cast<const float2 *>(&ring[rslot(t)][0][lane]);
+    const float2 a = q[1], b = q[129];
+    wu[0] = cg_f2{a.x, a.y};
+    wu[1] = cg_f2{b.x, b.y};
+  };
+  auto ld4 = [&](float4 (&rg)[4][64], int t) {
+    const float4 v = rg[t & 3][lane];
+    return cg_f4{v.x, v.y, v.z, v.w};
+  };
+  auto st4 = [&](float4 (&rg)[4][64], int t, cg_f4 v) { rg[t & 3][lane] = make_float4(v.x, v.y, v.z, v.w); };
+  auto load_po = [&](int t) { return FIRST ? cg_f4{0.f, 0.f, 0.f, 0.f} : cg_mask1<ODD>(cg_ld4(rpo, o8(t)), ok1); };
+  auto load_rin = [&](int t) { return cg_mask1<ODD>(cg_ld4(rin, o8(t)), ok1); };
+  // x_lo = 0 in the launch after a residual replacement (xz, known after
+  // the prologue; the preamble's x rows are then dropped)
+  bool xz = false;
+  // (always issued: outside the band, and after xz, from an out-of-range
+  // offset that returns 0 without memory traffic.  A branch around the load
+  // makes the count of memory operations behind an earlier load depend on
+  // the path, and the wait before that load's use then covers this step's)
+  auto load_x = [&](int t) {
+    if (FIRST) return cg_f4{0.f, 0.f, 0.f, 0.f};
+    return cg_mask1<ODD>(cg_ld4(rx, !xz && t >= r0 && t < r1 ? o8(t) : CG_OOB), ok1);
+  };
+  const bool dm0 = out_lane && ok0, dm1 = out_lane && ok1;
+  auto mdot = [&](cg_f4 a, cg_f4 b) {
+    const cg_f2 p = cg_lo(a) * cg_lo(b), q = cg_hi(a) * cg_hi(b);
+    return (dm0 ? p.x + p.y : 0.f) + (dm1 ? q.x + q.y : 0.f);
+  };
+  const cg_f4 zero4 = {0.f, 0.f, 0.f, 0.f};
+  const int ns = r0 - 8, ne = r1 + 11;
+
+  // zeroed rings: rows above the band that no required stage reads
+  {
+    float4 *z = &ring[0][0][0];
+    for (int e = tid; e < CGS_NREC * 4 * 64; e += 256) z[e] = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int e = tid; e < 8 * 64; e += 256) (&s_y[0][0])[e] = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int e = tid; e < 4 * 64; e += 256) {
+      (&s_g1[0][0])[e] = make_float4(0.f, 0.f, 0.f, 0.f);
+      (&s_yq[0][0])[e] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+  }
+  // wave 0: raw rows ns-2 .. ns+PF-1, p_old rows ns-2 .. ns+PF-1, r_in rows
+  // ns-1 .. ns+PF-2; wave 2: p_old, x of rows ns-8 .. ns-9+PF2 (register
+  // rings indexed by (row - ns) mod ring size)
+  CgRaw SG[CGS_SGN], SGp[2];
+  cg_f4 PO[8], RI[CGS_RIN], PO2[CGS_W2N], XI[CGS_W2N];
+  if (live && role == 0) {
+    load_raw(ns - 2, SGp[0]);
+    load_raw(ns - 1, SGp[1]);
+#pragma unroll
+    for (int m = 0; m < CGS_PF; ++m) load_raw(ns + m, SG[m]);
+    SG[CGS_SGN - 1] = SGp[1];  // raw row ns-1: stage A's D at the first step
+#pragma unroll
+    for (int m = -2; m < CGS_PF; ++m) PO[m & 7] = load_po(ns + m);
+#pragma unroll
+    for (int m = -1; m < CGS_PF - 1; ++m) RI[(m + 16) & (CGS_RIN - 1)] = load_rin(ns + m);
+  }
+  if (live && role == 2) {
+#pragma unroll
+    for (int m = -8; m < CGS_PF2 - 8; ++m) {
+      PO2[(m + 16) & (CGS_W2N - 1)] = load_po(ns + m);
+      XI[(m + 16) & (CGS_W2N - 1)] = load_x(ns + m);
+    }
+  }
+  float alpha = 0.f, beta = 0.f;
+  if (cg_prologue<FIRST>(g, k, lds, &alpha, &beta, &xz)) return;
+  if (xz)
+#pragma unroll
+    for (int m = 0; m < CGS_W2N; ++m) XI[m] = zero4;
+
+  double acc[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+  CgRec QA[2];  // CGS_W0REG: wave 0's records of rows n - 2, n - 1 (by R2)
+  // row o inside the band (stores and dot products only there); so8: the
+  // store offset of row o, out of range (the store is dropped) outside the
+  // band, so that every row step issues the same memory operations
+  auto inband = [&](int o) { return o >= r0 && o < r1; };
+  // (the empty asm keeps the select: without it the compiler threads the
+  // stores back into the two arms of the inband branch below them)
+  auto so8 = [&](int o) {
+    unsigned ro = inband(o) ? orow(o) * rowb8 : CG_ROW_OOB;
+    asm("" : "+s"(ro));
+    return soff8 + ro;
+  };
+  if (live) {
+    if (role == 0) {
+      QA[0] = put_rec(ns - 2, SGp[0]);  // ring slots of rows ns - 2, ns - 1 at u = 0
+      QA[1] = put_rec(ns - 1, SGp[1]);
+    }
+    __syncthreads();
+    CGS_T0
+    // issue priority for the pace-setting roles (loads + stage A, and z / p /
+    // q) over the Horner and T waves they share a SIMD with: 52 -> 50 us
+    // per 1080p launch (A/B, profiles/r2z_cgs_setprio_ab.log; wave 0
+    // alone: 51.3)
+    if (role == 0 || role == 2) __builtin_amdgcn_s_setprio(2);
+    // the Horner and T waves above other kernels' waves on their SIMD (the
+    // timed lanes run a fine solve one block per CU beside other lanes' work)
+    else __builtin_amdgcn_s_setprio(1);
+    // each wave runs its own role's loop (registers of one role only), one
+    // block barrier per row step in every role (same step count)
+#define CGS_STEPS(...)                                                    \
+  for (int n0 = ns; n0 <= ne; n0 += 8) {                                  \
+    _Pragma("unroll") for (int u = 0; u < 8; ++u) {                       \
+      const int n = n0 + u;                                               \
+      if (n > ne) break;                                                  \
+      __VA_ARGS__                                                         \
+      CGS_BAR_BEGIN                                                       \
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");              \
+      __builtin_amdgcn_s_barrier();                                       \
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");              \
+      CGS_BAR_END                                                         \
+    }                                                                     \
+  }
+// register-ring index of row n + d: (u + d) mod ring size
+#define R8(d) ((u + (d) + 16) & 7)
+#define R4(d) ((u + (d) + 16) & 3)
+#define R2(d) ((u + (d) + 16) & 1)
+#define RSG(d) ((u + (d) + 16) & (CGS_SGN - 1))
+#define RRI(d) ((u + (d) + 16) & (CGS_RIN - 1))
+#define RW2(d) ((u + (d) + 16) & (CGS_W2N - 1))
+    if (role == 0) {
+      CGS_STEPS({
+        load_raw(n + CGS_PF, SG[RSG(CGS_PF)]);
+        PO[R8(CGS_PF)] = load_po(n + CGS_PF);
+        RI[RRI(CGS_PF - 1)] = load_rin(n + CGS_PF - 1);
+        // A) row n-1: r = r_in - alpha A p_old, y = D^-1 r
+#if CGS_W0REG
+        const cg_f2 wu[2] = {QA[R2(-2)].wy[0], QA[R2(-2)].wy[1]};  // before row n takes the slot
+        const CgRec q1 = QA[R2(-1)];
+        QA[R2(0)] = put_rec(n, SG[RSG(0)]);
+#else
+        put_rec(n, SG[RSG(0)]);
+        const CgRec q1 = get_rec(n - 1);
+        cg_f2 wu[2];
+        get_wy(n - 2, wu);
+#endif
+        cg_f4 r = RI[RRI(-1)];
+        if (!FIRST) r -= alpha * (cgr_diag_raw(SG[RSG(-1)], PO[R8(-1)]) - cgr_nsum(PO[R8(-2)], PO[R8(-1)], PO[R8(0)], q1, wu));
+        const cg_f4 y = cgr_minv(q1, r);
+        s_y[(n - 1) & 7][lane] = make_float4(y.x, y.y, y.z, y.w);
+        const int o = n - 1;
+        cg_st4(rro, so8(o), r);
+        if (inband(o)) {
+          acc[4] += (double)mdot(r, r);
+          acc[3] += (double)(c0 * mdot(r, y));
+        }
+      })
+    } else if (role == 1) {
+      // Horner, degree 5: g4 = c4 y + c5 B y (row n-3), g3 = c3 y + B g4
+      // (n-4), g2 = c2 y + B g3 (n-5), g1 = c1 y + B g2 (n-6) -> LDS
+      cg_f4 G4[4] = {zero4, zero4, zero4, zero4}, G3[4] = {zero4, zero4, zero4, zero4};
+      cg_f4 G2[4] = {zero4, zero4, zero4, zero4};
+      auto yrow = [&](int t) {
+        const float4 a = s_y[t & 7][lane];
+        return cg_f4{a.x, a.y, a.z, a.w};
+      };
+#define CGS_REC1(d) get_rec(n + (d))
+#define CGS_WY1(d, w) \
+  cg_f2 w[2];         \
+  get_wy(n + (d), w)
+#define CGS_Y1(d) yrow(n + (d))
+      CGS_STEPS({
+        CGS_WY1(-7, w7);
+        {
+          const CgRec q = CGS_REC1(-3);
+          CGS_WY1(-4, wu);
+          const cg_f4 y0 = CGS_Y1(-3);
+          const cg_f4 ny = cgr_nsum(CGS_Y1(-4), y0, CGS_Y1(-2), q, wu);
+          G4[R4(-3)] = c4 * y0 + c5 * cgr_minv(q, ny);
+        }
+        {
+          const CgRec q = CGS_REC1(-4);
+          CGS_WY1(-5, wu);
+          const cg_f4 ng = cgr_nsum(G4[R4(-5)], G4[R4(-4)], G4[R4(-3)], q, wu);
+          G3[R4(-4)] = c3 * CGS_Y1(-4) + cgr_minv(q, ng);
+        }
+        {
+          const CgRec q = CGS_REC1(-5);
+          CGS_WY1(-6, wu);
+          const cg_f4 ng = cgr_nsum(G3[R4(-6)], G3[R4(-5)], G3[R4(-4)], q, wu);
+          G2[R4(-5)] = c2 * CGS_Y1(-5) + cgr_minv(q, ng);
+        }
+        {
+          const CgRec q = CGS_REC1(-6);
+          const cg_f4 ng = cgr_nsum(G2[R4(-7)], G2[R4(-6)], G2[R4(-5)], q, w7);
+          st4(s_g1, n - 6, c1 * CGS_Y1(-6) + cgr_minv(q, ng));
+        }
+      })
+#undef CGS_REC1
+#undef CGS_WY1
+#undef CGS_Y1
+    } else if (role == 2) {
+      cg_f4 PP[4] = {zero4, zero4, zero4, zero4}, ZZ[2] = {zero4, zero4};
+      CGS_STEPS({
+        PO2[RW2(CGS_PF2 - 8)] = load_po(n + CGS_PF2 - 8);
+        XI[RW2(CGS_PF2 - 8)] = load_x(n + CGS_PF2 - 8);
+        // D) row n-8: z = c0 y + D^-1 N g1, p = z + beta p_old, x += alpha p_old
+        {
+          const CgRec q4 = get_rec(n - 8);
+          cg_f2 wu[2];
+          get_wy(n - 9, wu);
+          const cg_f4 ng = cgr_nsum(ld4(s_g1, n - 9), ld4(s_g1, n - 8), ld4(s_g1, n - 7), q4, wu);
+          const float4 b = s_y[(n - 8) & 7][lane];
+          const cg_f4 yr = {b.x, b.y, b.z, b.w};
+          const cg_f4 z = c0 * yr + cgr_minv(q4, ng);
+          cg_f4 p = FIRST ? z : z + beta * PO2[RW2(-8)];
+          const int o = n - 8;
+          const bool rv = (unsigned)o < (unsigned)H;
+          if (!(rv && ok0)) { p.x = 0.f; p.y = 0.f; }
+          if (!(rv && ok1)) { p.z = 0.f; p.w = 0.f; }
+          PP[R4(-8)] = p;
+          ZZ[R2(-8)] = z;
+          const unsigned so = so8(o);
+          cg_st4(rpn, so, p);
+          cg_st4(rx, so, FIRST ? zero4 : XI[RW2(-8)] + alpha * PO2[RW2(-8)]);
+          if (inband(o)) acc[3] += (double)mdot(yr, ng);
+        }
+        // E) row n-9: q = A p, y_q = D^-1 q
+        {
+          const CgRec q5 = get_rec(n - 9);
+          cg_f2 wu[2];
+          get_wy(n - 10, wu);
+          const cg_f4 pm = PP[R4(-9)];
+          const cg_f4 q = cgr_diag(q5, pm) -
+                          cgr_nsum(PP[R4(-10)], pm, PP[R4(-8)], q5, wu);
+          const cg_f4 yq = cgr_minv(q5, q);
+          st4(s_yq, n - 9, yq);
+          const int o = n - 9;
+          if (inband(o)) {
+            acc[0] += (double)mdot(pm, q);
+            acc[1] += (double)mdot(q, ZZ[R2(-9)]);
+            acc[2] += (double)(c0 * mdot(q, yq));
+          }
+        }
+      })
+    } else {
+      // q.M^-1 q = sum_i c_i T_i with v0 = y_q, v1 = B v0, v2 = B v1:
+      // T1 = v0.N v0, T2 = v1.N v0 (row n-11); T3 = v1.N v1, T4 = v2.N v1,
+      // T5 = v2.N v2 (row n-12; T5 counts each edge once, by its right /
+      // lower pixel)
+      cg_f4 V1[4] = {zero4, zero4, zero4, zero4}, V2[2] = {zero4, zero4};
+      CGS_STEPS({
+        // row n's record: raw since wave 0 stored it at step n - 1; stage A
+        // reads it at step n + 1
+        {
+          const CgRec q6 = get_rec(n - 11);
+          cg_f2 wu[2];
+          get_wy(n - 12, wu);
+          const cg_f4 yq = ld4(s_yq, n - 11);
+          const cg_f4 ny = cgr_nsum(ld4(s_yq, n - 12), yq, ld4(s_yq, n - 10), q6, wu);
+          const cg_f4 v1 = cgr_minv(q6, ny);
+          V1[R4(-11)] = v1;
+          const int o = n - 11;
+          if (inband(o)) {
+            const cg_f4 t = (c1 * yq + c2 * v1) * ny;
+            acc[2] += (double)((dm0 ? t.x + t.y : 0.f) + (dm1 ? t.z + t.w : 0.f));
+          }
+        }
+        {
+          const CgRec q7 = get_rec(n - 12);
+          cg_f2 wy7[2];
+          get_wy(n - 13, wy7);
+          const cg_f4 v1 = V1[R4(-12)];
+          const cg_f4 nv = cgr_nsum(V1[R4(-13)], v1, V1[R4(-11)], q7, wy7);
+          const cg_f4 v2 = cgr_minv(q7, nv);
+          const cg_f4 vu = V2[R2(-13)];
+          V2[R2(-12)] = v2;
+          const int o = n - 12;
+          if (inband(o)) {
+            const cg_f2 w0 = cg_lo(v2), w1 = cg_hi(v2);
+            const cg_f2 h0 = cg_left2(q7.wx[1]) * cg_left2(w1) + wy7[0] * cg_lo(vu);
+            const cg_f2 h1 = q7.wx[0] * w0 + wy7[1] * cg_hi(vu);
+            const cg_f4 t = (c3 * v1 + c4 * v2) * nv + (2.0f * c5) * v2 * cg_cat(h0, h1);
+            acc[2] += (double)((dm0 ? t.x + t.y : 0.f) + (dm1 ? t.z + t.w : 0.f));
+          }
+        }
+      })
+    }
+#undef R8
+#undef R4
+#undef R2
+#undef RSG
+#undef RRI
+#undef RW2
+#undef CGS_STEPS
+    CGS_T1
+  }
+  write_partials<5>(acc, g.part_wr, lds);
+}

@@ -6,7 +6,10 @@
 // a fitted layer's inliers (k_layers_remove, k_layers_commit), the joint label
 // assignment with the per-layer state planes of the refits (k_layers_assign)
 // and the label mode filter (k_layers_mode).  The passes between them are the
-// fit's own kernels (kernels_motion.hip, included before this file), unchanged.
+// fit's own kernels (kernels_motion.hip, included before this file), unchanged,
+// and what these kernels do as the fit does it, they do with the fit's own
+// pieces: its tile mapping (MOT_TILE), usable-sample test (mot_usable), state
+// reset (mot_reset) and closed-form solve (mot_solve).
 // Same conventions as there: pitched float2 flows, dense H x W planes, fp64
 // from the fp32 inputs with no contraction in the order include/optflow.h
 // states ("Layered motion segmentation"); every floating-point sum in the
@@ -51,14 +54,6 @@ __device__ __forceinline__ double lay_r2(const double *th, double x, double y, d
 // the lanes of a wave for which p holds
 __device__ __forceinline__ int lay_votes(bool p) { return __popcll(__ballot(p)); }
 
-// k_motion_part's mapping: wave w of block b has tile b * MOT_WAVES + w, lane l
-// its column j, rows i0 .. i0 + 7
-#define LAY_TILE(ntx)                                                 \
-  const int lane = threadIdx.x & 63;                                  \
-  const int tile = blockIdx.x * MOT_WAVES + (threadIdx.x >> 6);       \
-  const int ty = tile / (ntx), tx = tile - ty * (ntx);                \
-  const int j = tx * MOT_TW + lane, i0 = ty * MOT_TH
-
 // state plane and count of the usable pixels: w0 > 0, with w0 the fit's
 __global__ void __launch_bounds__(MOT_WAVES * 64)
 k_layers_usable(const float2 *__restrict__ uv, int H, int W, int P, const float *__restrict__ wgt,
@@ -66,7 +61,7 @@ k_layers_usable(const float2 *__restrict__ uv, int H, int W, int P, const float 
   __shared__ int scnt;
   if (threadIdx.x == 0) scnt = 0;
   __syncthreads();
-  LAY_TILE(ntx);
+  MOT_TILE(ntx);
   if (tile < nt) {
     int cnt = 0;
 #pragma unroll
@@ -76,7 +71,7 @@ k_layers_usable(const float2 *__restrict__ uv, int H, int W, int P, const float 
       if (j < W && i < H) {
         const size_t o = (size_t)i * W + j;
         const float2 g = uv[(size_t)i * P + j];
-        const bool ok = __builtin_isfinite(g.x) && __builtin_isfinite(g.y) && (st ? st[o] : (uint8_t)0) == 0;
+        const bool ok = mot_usable(g, st ? st[o] : (uint8_t)0);
         use = ok && (wgt ? wgt[o] : 1.0f) > 0.0f;
         cst[o] = use ? LAY_REM : LAY_UNUSABLE;
       }
@@ -122,50 +117,6 @@ __device__ __forceinline__ double lay_cell_sum(const double *__restrict__ v, int
   return mot_tree(b4);
 }
 
-// k_motion_final's solve of one pass, operation for operation (that kernel
-// stays as it is, so its closed forms are written out a second time here): th
-// from the 13 sums (Sw > 0); true when the model lost rank and the translation
-// was solved
-__device__ __forceinline__ bool lay_solve(const double *S, int model, double *th) {
-  OF_NOCONTRACT
-  const double Sw = S[0], Sx = S[1], Sy = S[2], Sxx = S[3], Sxy = S[4], Syy = S[5];
-  const double Su = S[6], Sxu = S[7], Syu = S[8], Sv = S[9], Sxv = S[10], Syv = S[11];
-  th[0] = Su / Sw;
-  th[3] = Sv / Sw;
-  th[1] = th[2] = th[4] = th[5] = 0.0;
-  if (model == OF_MOTION_SIMILARITY) {
-    const double q = Sxx + Syy;
-    const double D = q - (Sx * Sx + Sy * Sy) / Sw;
-    if (!(D > 1e-9 * Sw)) return true;
-    const double ca = ((Sxu + Syv) - (Sx * Su + Sy * Sv) / Sw) / D;
-    const double cb = ((Sxv - Syu) - (Sx * Sv - Sy * Su) / Sw) / D;
-    th[0] = (Su - ca * Sx + cb * Sy) / Sw;
-    th[3] = (Sv - cb * Sx - ca * Sy) / Sw;
-    th[1] = ca;
-    th[5] = ca;
-    th[4] = cb;
-    th[2] = -cb;
-  } else if (model == OF_MOTION_AFFINE) {
-    const double m = Sx / Sw, nn = Sy / Sw;
-    const double A = Sxx - m * Sx, B = Sxy - m * Sy, Cc = Syy - nn * Sy;
-    const double l = B / A;
-    const double E = Cc - l * B;
-    if (!(A > 1e-9 * Sw) || !(E > 1e-9 * Sw)) return true;
-#pragma unroll
-    for (int f = 0; f < 2; ++f) {
-      const double Sf = f ? Sv : Su, Sxf = f ? Sxv : Sxu, Syf = f ? Syv : Syu;
-      const double gx = Sxf - m * Sf, gy = Syf - nn * Sf;
-      const double p2 = (gy - l * gx) / E;
-      const double p1 = (gx - B * p2) / A;
-      const double p0 = (Sf - Sx * p1 - Sy * p2) / Sw;
-      th[3 * f] = p0;
-      th[3 * f + 1] = p1;
-      th[3 * f + 2] = p2;
-    }
-  }
-  return false;
-}
-
 // One wave per cell (a, b) of the g x g grid over the nty x ntx tile records
 // of pass 0 (rec[k * stride + tile]): the cell's tiles in row-major order
 // through the group tree, then the solve in lane 0.
@@ -184,7 +135,7 @@ k_layers_cells(const double *__restrict__ rec, int stride, int nty, int ntx, int
     const int cwid = q1 - q0;
     for (int k = 0; k < MOT_NS; ++k)
       S[k] = lay_cell_sum(rec + (size_t)k * stride, ntx, r0, q0, cwid, (r1 - r0) * cwid, lane);
-    if (lane == 0 && S[0] > 0.0) flag = lay_solve(S, model, th) ? 3 : 1;
+    if (lane == 0 && S[0] > 0.0) flag = mot_solve(S, model, th) ? 3 : 1;
   }
   if (lane != 0) return;
   for (int k = 0; k < 6; ++k) hyp[cell].th[k] = th[k];
@@ -209,7 +160,7 @@ k_layers_score(const float2 *__restrict__ uv, int H, int W, int P, const uint8_t
     for (int k = 0; k < 6; ++k) sth[h * 6 + k] = hyp[h].th[k];
   }
   __syncthreads();
-  LAY_TILE(ntx);
+  MOT_TILE(ntx);
   if (tile < nt) {
     double u[MOT_TH], v[MOT_TH], y[MOT_TH];
     unsigned rem = 0;
@@ -264,13 +215,7 @@ k_layers_pick(const LayerHyp *__restrict__ hyp, int nh, int l, double min_suppor
     }
   }
   if (lane != 0) return;
-  for (int k = 0; k < 6; ++k) ms->th[k] = 0.0;
-  for (int k = 0; k < MOT_NS; ++k) ms->sums[k] = 0.0;
-  ms->c2 = c2;
-  ms->passes = 0;
-  ms->degenerate = 0;
-  ms->stop = 1;
-  ms->pad_ = 0;
+  mot_reset(ms, c2, 1);
   if (ctl->done) return;
   if (bh < 0 || (double)bc < min_support * (double)ctl->total) {
     ctl->done = 1;
@@ -291,7 +236,7 @@ k_layers_remove(const float2 *__restrict__ uv, int H, int W, int P, uint8_t *__r
   if (ctl->done) return;  // the whole grid
   if (threadIdx.x == 0) scnt = 0;
   __syncthreads();
-  LAY_TILE(ntx);
+  MOT_TILE(ntx);
   if (tile < nt) {
     double th[6];
     for (int k = 0; k < 6; ++k) th[k] = ms->th[k];
@@ -340,7 +285,7 @@ k_layers_assign(const float2 *__restrict__ uv, int H, int W, int P, const uint8_
   if ((int)threadIdx.x < n * 6) sth[threadIdx.x] = lay[threadIdx.x / 6].th[threadIdx.x % 6];
   if (blockIdx.x == 0 && (int)threadIdx.x < n) lay[threadIdx.x].stop = 0;
   __syncthreads();
-  LAY_TILE(ntx);
+  MOT_TILE(ntx);
   if (tile >= nt || j >= W) return;
   const size_t ps = (size_t)H * W;
   const double x = ((double)j - fr.cx) / fr.s;

@@ -12,6 +12,10 @@
 // the halving tree over its 64 columns, the same tree over groups of 64 tiles)
 // whatever the launch geometry: no atomics, nothing that depends on the order
 // of arrival.  H * W < 2^31 (checked on the host).
+// The arithmetic of a fit pass is stated once, here: the reset of a state
+// (mot_reset), the tile mapping (MOT_TILE), the usable-sample test
+// (mot_usable) and the closed-form solve (mot_solve) are what
+// kernels_layers.hip, included after this file, uses as well.
 #include "kernels.h"
 
 #define MOT_NS 13     // sums per pass: Sw Sx Sy Sxx Sxy Syy Su Sxu Syu Sv Sxv Syv Sr
@@ -50,15 +54,35 @@ __device__ __forceinline__ double mot_tree(double v) {
   return v;
 }
 
-__global__ void k_motion_init(MotionState *__restrict__ ms, double c2) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+// a fit's state before its first pass: nothing solved, the cutoff c2; stop 1
+// leaves the fit stopped, so that passes queued behind it do nothing
+__device__ __forceinline__ void mot_reset(MotionState *__restrict__ ms, double c2, int stop) {
   for (int k = 0; k < 6; ++k) ms->th[k] = 0.0;
   for (int k = 0; k < MOT_NS; ++k) ms->sums[k] = 0.0;
   ms->c2 = c2;
   ms->passes = 0;
   ms->degenerate = 0;
-  ms->stop = 0;
+  ms->stop = stop;
   ms->pad_ = 0;
+}
+
+__global__ void k_motion_init(MotionState *__restrict__ ms, double c2) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  mot_reset(ms, c2, 0);
+}
+
+// The tile mapping of every kernel that walks a plane in the fit's order: wave
+// w of block b has tile b * MOT_WAVES + w (row-major over ntx tiles across),
+// lane l its column j, rows i0 .. i0 + 7
+#define MOT_TILE(ntx)                                                 \
+  const int lane = threadIdx.x & 63;                                  \
+  const int tile = blockIdx.x * MOT_WAVES + (threadIdx.x >> 6);       \
+  const int ty = tile / (ntx), tx = tile - ty * (ntx);                \
+  const int j = tx * MOT_TW + lane, i0 = ty * MOT_TH
+
+// a sample the fit may use, whatever its weight: a finite flow and state 0
+__device__ __forceinline__ bool mot_usable(float2 g, uint8_t state) {
+  return __builtin_isfinite(g.x) && __builtin_isfinite(g.y) && state == 0;
 }
 
 // One wave per tile (tile = blockIdx.x * MOT_WAVES + wave, row-major over
@@ -73,12 +97,9 @@ k_motion_part(const float2 *__restrict__ uv, int H, int W, int P, const float *_
               const uint8_t *__restrict__ st, const MotionState *__restrict__ ms, int pass, MotionFrame fr, int ntx,
               int nt, int stride, double *__restrict__ rec, float *__restrict__ inl) {
   OF_NOCONTRACT
-  const int lane = threadIdx.x & 63;
-  const int tile = blockIdx.x * MOT_WAVES + (threadIdx.x >> 6);
+  MOT_TILE(ntx);
   if (tile >= nt) return;  // the whole wave
   if (pass != MOT_PASS_LAST && ms->stop) return;
-  const int ty = tile / ntx, tx = tile - ty * ntx;
-  const int j = tx * MOT_TW + lane, i0 = ty * MOT_TH;
   const bool jin = j < W;
   const double th0 = ms->th[0], th1 = ms->th[1], th2 = ms->th[2], th3 = ms->th[3], th4 = ms->th[4], th5 = ms->th[5];
   const double c2 = ms->c2;
@@ -102,7 +123,7 @@ k_motion_part(const float2 *__restrict__ uv, int H, int W, int P, const float *_
   for (int r = 0; r < MOT_TH; ++r) {
     const int i = i0 + r;
     if (!(jin && i < H)) continue;
-    const bool ok = __builtin_isfinite(g[r].x) && __builtin_isfinite(g[r].y) && s8[r] == 0;
+    const bool ok = mot_usable(g[r], s8[r]);
     const double w0 = ok ? (double)w32[r] : 0.0;
     const double u = ok ? (double)g[r].x : 0.0, v = ok ? (double)g[r].y : 0.0;
     const double y = ((double)i - fr.cy) / fr.s;
@@ -155,11 +176,55 @@ k_motion_group(const double *__restrict__ src, int n, int sstride, double *__res
   }
 }
 
+// The solve of one pass in the closed forms of include/optflow.h, operation
+// for operation: th from the 13 sums (Sw > 0); true when the model lost rank
+// and the translation was solved.  The one statement of it: the fit
+// (k_motion_final) and the layers' hypotheses (k_layers_cells) both call it.
+__device__ __forceinline__ bool mot_solve(const double *S, int model, double *th) {
+  OF_NOCONTRACT
+  const double Sw = S[0], Sx = S[1], Sy = S[2], Sxx = S[3], Sxy = S[4], Syy = S[5];
+  const double Su = S[6], Sxu = S[7], Syu = S[8], Sv = S[9], Sxv = S[10], Syv = S[11];
+  th[0] = Su / Sw;  // the translation model
+  th[3] = Sv / Sw;
+  th[1] = th[2] = th[4] = th[5] = 0.0;
+  if (model == OF_MOTION_SIMILARITY) {
+    const double q = Sxx + Syy;
+    const double D = q - (Sx * Sx + Sy * Sy) / Sw;
+    if (!(D > 1e-9 * Sw)) return true;
+    const double ca = ((Sxu + Syv) - (Sx * Su + Sy * Sv) / Sw) / D;
+    const double cb = ((Sxv - Syu) - (Sx * Sv - Sy * Su) / Sw) / D;
+    th[0] = (Su - ca * Sx + cb * Sy) / Sw;
+    th[3] = (Sv - cb * Sx - ca * Sy) / Sw;
+    th[1] = ca;
+    th[5] = ca;
+    th[4] = cb;
+    th[2] = -cb;
+  } else if (model == OF_MOTION_AFFINE) {
+    const double m = Sx / Sw, nn = Sy / Sw;
+    const double A = Sxx - m * Sx, B = Sxy - m * Sy, Cc = Syy - nn * Sy;
+    const double l = B / A;
+    const double E = Cc - l * B;
+    if (!(A > 1e-9 * Sw) || !(E > 1e-9 * Sw)) return true;
+#pragma unroll
+    for (int f = 0; f < 2; ++f) {
+      const double Sf = f ? Sv : Su, Sxf = f ? Sxv : Sxu, Syf = f ? Syv : Syu;
+      const double gx = Sxf - m * Sf, gy = Syf - nn * Sf;
+      const double p2 = (gy - l * gx) / E;
+      const double p1 = (gx - B * p2) / A;
+      const double p0 = (Sf - Sx * p1 - Sy * p2) / Sw;
+      th[3 * f] = p0;
+      th[3 * f + 1] = p1;
+      th[3 * f + 2] = p2;
+    }
+  }
+  return false;
+}
+
 // The last level (n <= 64 values per sum, one wave), then in lane 0 the solve
 // of the pass and the cutoff update: th and c2 stay in device memory for the
 // next pass, so a whole fit is a chain of launches with one read-back at its
-// end.  The closed forms are those of include/optflow.h, operation for
-// operation.  kappa2 = kappa * kappa and cmin2 = c_min * c_min from the host.
+// end.  The solve is mot_solve.  kappa2 = kappa * kappa and cmin2 = c_min *
+// c_min from the host.
 __global__ void __launch_bounds__(64)
 k_motion_final(const double *__restrict__ src, int n, int sstride, MotionState *__restrict__ ms, int pass, int model,
                double kappa2, double decay, double cmin2) {
@@ -173,52 +238,15 @@ k_motion_final(const double *__restrict__ src, int n, int sstride, MotionState *
 #pragma unroll
   for (int k = 0; k < MOT_NS; ++k) ms->sums[k] = S[k];
   if (pass == MOT_PASS_LAST) return;
-  const double Sw = S[0], Sx = S[1], Sy = S[2], Sxx = S[3], Sxy = S[4], Syy = S[5];
-  const double Su = S[6], Sxu = S[7], Syu = S[8], Sv = S[9], Sxv = S[10], Syv = S[11], Sr = S[12];
+  const double Sw = S[0], Sr = S[12];
   ms->passes += 1;
   if (!(Sw > 0.0)) {
     ms->stop = 1;
     ms->degenerate |= 2;
     return;
   }
-  double th[6] = {Su / Sw, 0.0, 0.0, Sv / Sw, 0.0, 0.0};  // the translation model
-  bool lost = false;
-  if (model == OF_MOTION_SIMILARITY) {
-    const double q = Sxx + Syy;
-    const double D = q - (Sx * Sx + Sy * Sy) / Sw;
-    if (!(D > 1e-9 * Sw)) {
-      lost = true;
-    } else {
-      const double ca = ((Sxu + Syv) - (Sx * Su + Sy * Sv) / Sw) / D;
-      const double cb = ((Sxv - Syu) - (Sx * Sv - Sy * Su) / Sw) / D;
-      th[0] = (Su - ca * Sx + cb * Sy) / Sw;
-      th[3] = (Sv - cb * Sx - ca * Sy) / Sw;
-      th[1] = ca;
-      th[5] = ca;
-      th[4] = cb;
-      th[2] = -cb;
-    }
-  } else if (model == OF_MOTION_AFFINE) {
-    const double m = Sx / Sw, nn = Sy / Sw;
-    const double A = Sxx - m * Sx, B = Sxy - m * Sy, Cc = Syy - nn * Sy;
-    const double l = B / A;
-    const double E = Cc - l * B;
-    if (!(A > 1e-9 * Sw) || !(E > 1e-9 * Sw)) {
-      lost = true;
-    } else {
-#pragma unroll
-      for (int f = 0; f < 2; ++f) {
-        const double Sf = f ? Sv : Su, Sxf = f ? Sxv : Sxu, Syf = f ? Syv : Syu;
-        const double gx = Sxf - m * Sf, gy = Syf - nn * Sf;
-        const double p2 = (gy - l * gx) / E;
-        const double p1 = (gx - B * p2) / A;
-        const double p0 = (Sf - Sx * p1 - Sy * p2) / Sw;
-        th[3 * f] = p0;
-        th[3 * f + 1] = p1;
-        th[3 * f + 2] = p2;
-      }
-    }
-  }
+  double th[6];
+  const bool lost = mot_solve(S, model, th);
   if (lost) ms->degenerate |= 1;
 #pragma unroll
   for (int k = 0; k < 6; ++k) ms->th[k] = th[k];

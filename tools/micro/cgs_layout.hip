@@ -14,6 +14,8 @@
 #include <vector>
 #include <algorithm>
 #include "kernels_solve.hip"
+#include "kernels_cg.hip"
+#include "kernels_cgs.hip"
 
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("HIP %s line %d\n", hipGetErrorString(e_), __LINE__); exit(1); } } while (0)
 

@@ -1,8 +1,10 @@
 """(The flow perturbation below varies by row only, which biases the robust
-weights towards horizontal coupling; see CGS_PAIR in kernels_solve.hip for the
-GPU measurement.)  CG iterations to 1e-6 relative residual with the degree-5 Chebyshev
-polynomial preconditioner in the 2x2 block-Jacobi splitting (k_cgs before
-CGS_PAIR) vs the pair-block splitting (4x4 blocks of the horizontal pixel
+weights towards horizontal coupling; the GPU measurement of the pair-block
+variant of k_cgs, a rejected switch called CGS_PAIR whose source has been
+removed, is in DESIGN.md, "Fused CG iteration": -6 % iterations for +7 % per
+launch.)  CG iterations to 1e-6 relative residual with the degree-5 Chebyshev
+polynomial preconditioner in the 2x2 block-Jacobi splitting (k_cgs as it
+is) vs the pair-block splitting (4x4 blocks of the horizontal pixel
 pairs (2k, 2k+1), the edge inside a pair moved into the block) on a
 Classic+NL-fast operator assembled by the float64 oracle (synthetic pair,
 texture images, perturbed ground-truth flow), quadratic (alpha 1) and
