@@ -661,6 +661,85 @@ int of_denoise_flush(of_ctx *ctx, float *out, float *out_weight, int32_t *out_in
 int of_denoise_close(of_ctx *ctx);
 
 /*
+ * Noise-level estimation: the standard deviation sigma of additive Gaussian
+ * noise, per channel and pooled, as the median absolute value of a residual
+ * that holds noise of a known variance factor and little else.  The pair
+ * estimator's residual is a pixel minus its motion-compensated partner in the
+ * other frame (the median ignores the minority where the flow is wrong); the
+ * single-frame estimator's is the diagonal Haar detail of 2 x 2 blocks.
+ * Everything in double from the fp32 inputs, no fma contraction, in exactly
+ * the order written; bil's taps and inside as defined above ("Using a flow on
+ * an image"); images H x W x C interleaved, C 1..4, the flow planar 2 x H x W,
+ * the state H x W bytes in of_fb_consistency's encoding.  H * W >= 2^31:
+ * OF_ENOTSUP.
+ *
+ * of_estimate_noise_pair: fw is the flow im1 -> im2, state its forward-
+ * backward state or NULL (all 0).  Pixel (i, j), (u, v) = fw(i, j), is usable
+ * when u and v are finite, inside(i + v, j + u), state(i, j) == 0 and, with
+ * the taps of bil at r = i + v, q = j + u (rows i0, i1, columns j0, j1,
+ * fractions fr, fc), im1_c(i, j) and the four values im2_c(i0|i1, j0|j1) are
+ * finite for every channel c.  Then
+ *   w00 = (1 - fr)*(1 - fc); w01 = (1 - fr)*fc; w10 = fr*(1 - fc); w11 = fr*fc
+ *   g = 1.0 + (((w00*w00 + w01*w01) + w10*w10) + w11*w11)
+ *   e_c = im1_c(i, j) - bil(im2_c, r, q)
+ *   key_c = (float)(e_c*e_c/g)
+ * g is the variance factor of "own noise + interpolated noise" (2 at integer
+ * flows, 1.25 at half-pixel ones), so the estimate does not depend on the
+ * sub-pixel phase.  The bilinear sample interpolates the signal too: while
+ * sigma is below the picture's interpolation error the estimate reads high.
+ *
+ * of_estimate_noise: the floor(H/2) x floor(W/2) non-overlapping 2 x 2 blocks
+ * (an odd last row or column is left out); H or W below 2: OF_EINVAL.  Block
+ * (bi, bj) with a = im_c(2bi, 2bj), b = im_c(2bi, 2bj+1), p = im_c(2bi+1, 2bj),
+ * q = im_c(2bi+1, 2bj+1) is usable when all four are finite for every c; then
+ *   d = ((a - b) - (p - q))/2.0;  key_c = (float)(d*d)
+ *
+ * Both: n = the usable pixels / blocks (every channel has n keys).  A key that
+ * rounds to +Inf stays in as +Inf.  Per channel m_c = the lower median of the
+ * n keys, the key of rank (n - 1)/2 (integer division, 0-based, ascending),
+ * selected exactly (a radix selection over the keys' bit patterns with integer
+ * counts: no dependence on launch geometry or arrival order), and on the host
+ *   sigma_c = sqrt((double)m_c)/0.6744897501960817
+ *   s = 0; c ascending: s += sigma_c*sigma_c;   sigma = sqrt(s/C)
+ * sigma_c[C..3] are NaN.  n == 0: every sigma NaN, n = 0, OF_OK.  Device
+ * scratch: the keys, 4*C*n_slots bytes of the arena (n_slots = H*W, or the
+ * blocks), and 32 KB + 64 bytes of counters kept with the context.
+ */
+typedef struct of_noise_estimate {
+  double sigma;       /* pooled over the channels */
+  double sigma_c[4];  /* per channel */
+  int64_t n;          /* samples per channel */
+} of_noise_estimate;
+int of_estimate_noise_pair(of_ctx *ctx, const float *im1, const float *im2, int H, int W, int C, const float *fw,
+                           const uint8_t *state, of_noise_estimate *out);
+int of_estimate_noise(of_ctx *ctx, const float *im, int H, int W, int C, of_noise_estimate *out);
+/*
+ * The denoiser session with an estimated sigma.  of_denoise_open_auto is
+ * of_denoise_open except that opts->sigma is not read (the other options are
+ * checked as there) and every emitted frame is fused with a sigma of its own;
+ * `floor`, finite and > 0, in image units, is the smallest one used (clean
+ * 8-bit material estimates 0, which the fusion refuses).  Every push that
+ * completes a pair (k-1, k) runs of_estimate_noise_pair once on the two frames
+ * as pushed, the pair's forward flow and its state, all still on the device,
+ * and keeps the result E_{k-1} on the host.  For the emitted frame t
+ *   s = 0; m = 0
+ *   j = t-1, then t, where pair (j, j+1) exists among the frames pushed so
+ *   far and 4*E_j.n >= H*W (a scene cut leaves few consistent pixels and must
+ *   not set the level):  s += E_j.sigma*E_j.sigma; m += 1
+ *   m > 0:                 sigma_t = sqrt(s/m)
+ *   m == 0, H, W >= 2:     sigma_t = of_estimate_noise(frame t).sigma
+ *   otherwise:             sigma_t = floor
+ *   !(sigma_t >= floor):   sigma_t = floor          (a NaN estimate too)
+ * and the fusion is of_fuse_frames with sigma = sigma_t, radius 2 included.
+ * of_denoise_last_sigma: the sigma the last emitted frame was fused with (of a
+ * session of either kind; opts->sigma for of_denoise_open); no session, or no
+ * frame emitted yet: OF_EINVAL.
+ */
+int of_denoise_open_auto(of_ctx *ctx, const of_params *params, int H, int W, int C, const of_fuse_opts *opts,
+                         double floor);
+int of_denoise_last_sigma(of_ctx *ctx, double *sigma);
+
+/*
  * Global motion estimation and video stabilisation.  The dominant (camera)
  * motion of a flow field is fitted as a translation, a similarity or an
  * affine map by iteratively reweighted least squares with Tukey's biweight

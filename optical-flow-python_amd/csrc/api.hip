@@ -102,6 +102,7 @@ int of_ctx_destroy(of_ctx *c) {
   hipFree(c->d_rpart);
   hipFree(c->d_rlog);
   hipFree(c->d_mm);
+  if (c->d_noise) hipFree(c->d_noise);
   hipFree(c->d_norm);
   hipHostFree(c->h_norm);
   if (c->stream) hipStreamDestroy(c->stream);

@@ -16,6 +16,7 @@
 //   kernels_flow.hip   warp, derivatives, system assembly, occlusion, medians, weighted median
 //   kernels_track.hip  point tracker: advance and seed steps
 //   kernels_fuse.hip   temporal denoising: flow composition, frame fusion
+//   kernels_noise.hip  noise-level estimation: the two estimators' keys, the exact radix selection of their median
 //   kernels_motion.hip global motion: the passes of the robust parametric fit, the affine warp
 //   kernels_layers.hip layered motion segmentation (uses the fit's passes)
 //   kernels_solve.hip  what the solvers share (partials, fixed-order sums, residual), norm and residual diagnostics
@@ -33,7 +34,8 @@
 //   host_flow.hip   assembly dispatch, token, per-level IRLS loops, schedule, estimate_*
 //   host_session.hip what the frame-sequence sessions share: lookup and free, open and push prologues, delayed emission
 //   host_track.hip  point tracker: advance and seed steps, stage entries, the session
-//   host_fuse.hip   temporal denoising: flow composition, frame fusion, stage entries, the session
+//   host_noise.hip  noise-level estimation: the pair and single-frame estimators, their stage entries
+//   host_fuse.hip   temporal denoising: flow composition, frame fusion, stage entries, the session and its automatic sigma
 //   host_motion.hip global motion: the robust parametric fit, the affine warp, path smoothing, the stabiliser session
 //   host_layers.hip layered motion segmentation: hypotheses, extraction, joint rounds, the stage entry
 //   batch.hip       lanes, of_pairs_run[_host], pair pool, slot copies, RCCL gather
@@ -60,6 +62,7 @@
 #include "kernels_flow.hip"
 #include "kernels_track.hip"
 #include "kernels_fuse.hip"
+#include "kernels_noise.hip"
 #include "kernels_motion.hip"
 #include "kernels_layers.hip"
 #include "kernels_solve.hip"
@@ -75,6 +78,7 @@
 #include "host_flow.hip"
 #include "host_session.hip"
 #include "host_track.hip"
+#include "host_noise.hip"
 #include "host_fuse.hip"
 #include "host_motion.hip"
 #include "host_layers.hip"

@@ -210,6 +210,13 @@ struct Denoiser : Session {
   of_fuse_opts opt;
   float2 *fw[4] = {}, *bw[4] = {};         // pair (j, j+1) at j % 2R: pitched flows j -> j+1 and j+1 -> j
   uint8_t *sf[4] = {}, *sb[4] = {};        // their forward-backward states, H x W dense
+  // of_denoise_open_auto: sigma per emitted frame from the pair estimates
+  // (host_noise.hip), kept on the host in the pairs' ring order
+  bool auto_sigma = false;
+  double floor = 0;                        // the smallest sigma a frame is fused with
+  of_noise_estimate est[4] = {};           // pair (j, j+1) at j % 2R
+  double last_sigma = 0;                   // what the last emitted frame was fused with
+  bool emitted = false;
 };
 
 // the stabiliser (of_stab_open, host_motion.hip): a ring of R+1 frames; the
@@ -336,6 +343,7 @@ struct of_ctx {
   bool slog_iter = false;  // ... whose iterate residual the solver logged itself
   double *d_rpart = nullptr, *d_rlog = nullptr;
   uint32_t *d_mm = nullptr;  // 32 min/max pairs
+  NoiseSel *d_noise = nullptr;  // the noise estimators' selection words (lazily allocated)
   double *d_norm = nullptr, *h_norm = nullptr;
   int prof = 0;  // 0 off, 1 per kernel, 2 per kernel and level ("name@pixels")
   std::vector<hipEvent_t> ev_pool;  // profiling events

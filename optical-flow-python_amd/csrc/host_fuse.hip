@@ -44,6 +44,34 @@ void fuse_dev(of_ctx *c, const float *center, int H, int W, int C, int P, int n,
          o.patch, two_s2, h2, gx, out, out_w);
 }
 
+// The sigma frame t of an automatic session is fused with: the root mean
+// square of the estimates of its adjacent pairs (t-1, t) and (t, t+1), those
+// that exist and rest on at least a quarter of the pixels (a scene cut leaves
+// few consistent ones); with neither, the single-frame estimate of frame t
+// (one more selection and read-back), or the floor where the frame has no
+// 2 x 2 block; never below the floor.
+double denoise_auto_sigma(of_ctx *c, Denoiser *d, int t) {
+  const int H = d->H, W = d->W, NP = 2 * d->opt.radius;
+  double s = 0.0;
+  int m = 0;
+  for (int j = t - 1; j <= t; ++j) {
+    if (j < 0 || j + 1 >= d->frames) continue;
+    const of_noise_estimate &e = d->est[j % NP];
+    if (4 * e.n < (int64_t)H * W) continue;
+    s = s + e.sigma * e.sigma;
+    ++m;
+  }
+  double sigma = d->floor;
+  if (m > 0) {
+    sigma = std::sqrt(s / (double)m);
+  } else if (H >= 2 && W >= 2) {
+    of_noise_estimate e;
+    noise_single_dev(c, d->frame[t % (int)d->frame.size()], H, W, d->C, &e);
+    sigma = e.sigma;
+  }
+  return sigma >= d->floor ? sigma : d->floor;  // a NaN (no usable block) gives the floor too
+}
+
 // Frame t of the session fused with the neighbours at offsets -1, +1, -2, +2
 // that exist among the frames pushed so far (|offset| <= radius), written to
 // the host buffers.  Offsets of 2 chain two adjacent pairs' flows.
@@ -85,6 +113,10 @@ void denoise_emit(of_ctx *c, Denoiser *d, int t, float *out, float *out_weight) 
       ++n;
     }
   const float *center = d->frame[t % NF];
+  of_fuse_opts opt = d->opt;
+  if (d->auto_sigma) opt.sigma = denoise_auto_sigma(c, d, t);
+  d->last_sigma = opt.sigma;
+  d->emitted = true;
   if (n == 0) {  // a clip of one frame
     download_dense(c, out, center, px * C);
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -92,10 +124,28 @@ void denoise_emit(of_ctx *c, Denoiser *d, int t, float *out, float *out_weight) 
     return;
   }
   float *dout = new_dense<float>(c, px * C), *dw = new_dense<float>(c, px, out_weight);
-  fuse_dev(c, center, H, W, C, d->pitch, n, neigh, flow, state, d->opt, dout, dw);
+  fuse_dev(c, center, H, W, C, d->pitch, n, neigh, flow, state, opt, dout, dw);
   download_dense(c, out, dout, px * C);
   download_dense(c, out_weight, dw, px);
   HIPCHK(hipStreamSynchronize(c->stream));
+}
+
+// of_denoise_open and of_denoise_open_auto: the session and its rings
+void denoise_open(of_ctx *c, const of_params *P, int H, int W, int C, const of_fuse_opts *o, bool auto_sigma,
+                  double floor) {
+  session_open<Denoiser>(c, SES_DENOISE, P, H, W, C, o, check_fuse_opts, [&](Denoiser *d) {
+    d->pitch = of_pitch(W);
+    d->auto_sigma = auto_sigma;
+    d->floor = floor;
+    const size_t px = (size_t)H * W, fpx = (size_t)H * d->pitch;
+    d->alloc_frames(2 * o->radius + 1);
+    for (int k = 0; k < 2 * o->radius; ++k) {
+      d->fw[k] = d->alloc<float2>(fpx);
+      d->bw[k] = d->alloc<float2>(fpx);
+      d->sf[k] = d->alloc<uint8_t>(px);
+      d->sb[k] = d->alloc<uint8_t>(px);
+    }
+  });
 }
 
 }  // namespace
@@ -150,18 +200,30 @@ int of_fuse_frames(of_ctx *c, const float *center, int H, int W, int C, int n, c
 
 int of_denoise_open(of_ctx *c, const of_params *P, int H, int W, int C, const of_fuse_opts *o) {
   API_BEGIN(c)
-  session_open<Denoiser>(c, SES_DENOISE, P, H, W, C, o, check_fuse_opts, [&](Denoiser *d) {
-    d->pitch = of_pitch(W);
-    const size_t px = (size_t)H * W, fpx = (size_t)H * d->pitch;
-    d->alloc_frames(2 * o->radius + 1);
-    for (int k = 0; k < 2 * o->radius; ++k) {
-      d->fw[k] = d->alloc<float2>(fpx);
-      d->bw[k] = d->alloc<float2>(fpx);
-      d->sf[k] = d->alloc<uint8_t>(px);
-      d->sb[k] = d->alloc<uint8_t>(px);
-    }
-  });
+  denoise_open(c, P, H, W, C, o, false, 0.0);
   API_END(c)
+}
+
+int of_denoise_open_auto(of_ctx *c, const of_params *P, int H, int W, int C, const of_fuse_opts *o, double floor) {
+  API_BEGIN(c)
+  REQUIRE(o, OF_EINVAL, "no fuse options");
+  REQUIRE(std::isfinite(floor) && floor > 0, OF_EINVAL, "the noise floor must be finite and > 0");
+  of_fuse_opts a = *o;
+  a.sigma = floor;  // the caller's sigma is not read; the checks see a valid one
+  denoise_open(c, P, H, W, C, &a, true, floor);
+  API_END(c)
+}
+
+int of_denoise_last_sigma(of_ctx *c, double *sigma) {
+  if (!c) return OF_EINVAL;
+  try {
+    Denoiser *d = session_get<Denoiser>(c, SES_DENOISE);
+    REQUIRE(sigma, OF_EINVAL, "bad arguments");
+    REQUIRE(d->emitted, OF_EINVAL, "the temporal denoiser has not emitted a frame yet");
+    *sigma = d->last_sigma;
+    return OF_OK;
+  }
+  API_CATCH(c)
 }
 
 int of_denoise_push(of_ctx *c, const float *frame, float *out, float *out_weight, int32_t *out_index) {
@@ -175,6 +237,10 @@ int of_denoise_push(of_ctx *c, const float *frame, float *out, float *out_weight
     const size_t fb = sizeof(float2) * (size_t)d->H * pr.fw.P;  // new_f2's pitch is of_pitch(W), the ring's
     HIPCHK(hipMemcpyAsync(d->fw[p], pr.fw.p, fb, hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(d->bw[p], pr.bw.p, fb, hipMemcpyDeviceToDevice, c->stream));
+    // the pair's noise level, from what is still on the device: frames k-1 and k, the forward flow and its state
+    if (d->auto_sigma)
+      noise_pair_dev(c, d->frame[(k - 1) % (int)d->frame.size()], pr.cur, d->H, d->W, d->C, pr.fw.p, pr.fw.P, d->sf[p],
+                     &d->est[p]);
   }
   *out_index = -1;
   const int t = session_next_emit(d, R, false);

@@ -10,6 +10,7 @@ from optical_flow.interface import (estimate_flow, estimate_flow_batch, PairStre
 from optical_flow.tracking import (advance_points, seed_points, PointTracker, track_points, Trajectories,
                                    TRACK_ALIVE, TRACK_OCCLUDED, TRACK_LEFT_FRAME, TRACK_MOTION_BOUNDARY)
 from optical_flow.temporal import compose_flows, fuse_frames, TemporalDenoiser, denoise_frames
+from optical_flow.noise import estimate_noise, NoiseEstimate
 from optical_flow.motion import (fit_motion, warp_affine, Stabilizer, stabilize_frames, MotionFit, segment_motion,
                                  MotionLayers, MotionLayer, LAYER_NONE)
 from optical_flow.utils.warping import warp_image
@@ -27,4 +28,4 @@ __all__ = ['estimate_flow', 'estimate_flow_batch', 'PairStream', 'read_flo', 'wr
            'seed_points', 'PointTracker', 'track_points', 'Trajectories', 'TRACK_ALIVE', 'TRACK_OCCLUDED',
            'TRACK_LEFT_FRAME', 'TRACK_MOTION_BOUNDARY', 'compose_flows', 'fuse_frames', 'TemporalDenoiser',
            'denoise_frames', 'fit_motion', 'warp_affine', 'Stabilizer', 'stabilize_frames', 'MotionFit',
-           'segment_motion', 'MotionLayers', 'MotionLayer', 'LAYER_NONE']
+           'segment_motion', 'MotionLayers', 'MotionLayer', 'LAYER_NONE', 'estimate_noise', 'NoiseEstimate']

@@ -145,6 +145,14 @@ class OfFuseOpts(C.Structure):
                 ("alpha1", C.c_double), ("alpha2", C.c_double)]
 
 
+# noise-level estimation (include/optflow.h, "Noise-level estimation")
+NOISE_MAX_CHANNELS = 4
+
+
+class OfNoiseEstimate(C.Structure):
+    _fields_ = [("sigma", C.c_double), ("sigma_c", C.c_double * 4), ("n", C.c_int64)]
+
+
 # global motion and stabilisation (include/optflow.h, "Global motion estimation")
 MOTION_MODEL = {"translation": 0, "similarity": 1, "affine": 2}
 MOTION_MAX_ITERS = 64

@@ -11,7 +11,7 @@ import threading
 import numpy as np
 
 from optical_flow._abi import (OfParams, OfStats, OfCgGeometry, OfSolveRecord, OfProgressFn, OfTrackOpts, OfFuseOpts,
-                               OfMotionOpts, OfMotionFit, OfStabOpts, OfLayersOpts, OfMotionLayer, OF_ABI_VERSION,
+                               OfNoiseEstimate, OfMotionOpts, OfMotionFit, OfStabOpts, OfLayersOpts, OfMotionLayer, OF_ABI_VERSION,
                                OF_EINVAL, OF_ENOTSUP)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -78,6 +78,12 @@ _SIGS = {
     "of_denoise_push": ([_vp, _fp, _fp, _fp, _i32p], C.c_int),
     "of_denoise_flush": ([_vp, _fp, _fp, _i32p], C.c_int),
     "of_denoise_close": ([_vp], C.c_int),
+    "of_estimate_noise_pair": ([_vp, _fp, _fp, C.c_int, C.c_int, C.c_int, _fp, _u8p, C.POINTER(OfNoiseEstimate)],
+                               C.c_int),
+    "of_estimate_noise": ([_vp, _fp, C.c_int, C.c_int, C.c_int, C.POINTER(OfNoiseEstimate)], C.c_int),
+    "of_denoise_open_auto": ([_vp, C.POINTER(OfParams), C.c_int, C.c_int, C.c_int, C.POINTER(OfFuseOpts),
+                              C.c_double], C.c_int),
+    "of_denoise_last_sigma": ([_vp, _dp], C.c_int),
     "of_fit_motion": ([_vp, _fp, C.c_int, C.c_int, _fp, _u8p, C.POINTER(OfMotionOpts), C.POINTER(OfMotionFit), _fp],
                       C.c_int),
     "of_warp_affine": ([_vp, _fp, C.c_int, C.c_int, C.c_int, _dp, _fp, _u8p], C.c_int),

@@ -110,9 +110,13 @@ class Session(Closing):
         P = method_params(method, params)[1]
         self.frames = 0
         ctx = nat.context() if context is None else context
-        ctx.check(getattr(ctx.lib, self._PREFIX + "open")(ctx.handle, C.byref(P), self.H, self.W, self.channels,
-                                                          C.byref(self._opts)))
+        ctx.check(self._open(ctx, P))
         self._ctx = ctx
+
+    def _open(self, ctx, P):
+        """The return code of the session's open entry on `ctx`."""
+        return getattr(ctx.lib, self._PREFIX + "open")(ctx.handle, C.byref(P), self.H, self.W, self.channels,
+                                                       C.byref(self._opts))
 
     def _live(self):
         if self._ctx is None:
@@ -160,16 +164,21 @@ class DelayedSession(Session):
     def run_clip(cls, frames, last, *args):
         """`frames` through a session cls(shape, *args): the frames it returns,
         (T, H, W[, 3]) float64, and the session's attribute `last` after each,
-        stacked, both by frame index."""
+        stacked, both by frame index; for a tuple of attribute names, a tuple
+        of such stacks."""
         frames = _clip(frames)
         out = np.empty((len(frames),) + frames[0].shape, dtype=np.float64)
-        extra = [None] * len(frames)
+        names = (last,) if isinstance(last, str) else tuple(last)
+        extra = [[None] * len(frames) for _ in names]
         with cls(frames[0].shape, *args) as s:
             def take(r):
                 if r is not None:
-                    out[r[0]], extra[r[0]] = r[1], getattr(s, last)
+                    out[r[0]] = r[1]
+                    for e, name in zip(extra, names):
+                        e[r[0]] = getattr(s, name)
             for f in frames:
                 take(s.push(f))
             for r in s.flush():
                 take(r)
-        return out, np.stack(extra)
+        stacks = tuple(np.stack(e) for e in extra)
+        return out, (stacks[0] if isinstance(last, str) else stacks)

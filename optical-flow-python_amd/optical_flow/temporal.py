@@ -17,11 +17,18 @@ from optical_flow import _native as nat
 from optical_flow._session import DelayedSession, _flow, _frame_size, _int_in, _number, _planar32, _state
 
 
+AUTO = "auto"  # sigma=AUTO: the session estimates the noise level itself (of_denoise_open_auto)
+
+
+def _is_auto(sigma):
+    return isinstance(sigma, str) and sigma == AUTO
+
+
 def _fuse_opts(sigma, radius=1, strength=4.0, patch=2, alpha1=0.01, alpha2=0.5):
     """of_fuse_opts from the keyword arguments; ValueError for anything the
     library would refuse (ranges of include/optflow.h)."""
     if sigma is None:
-        raise ValueError("sigma (the noise standard deviation in image units) is required")
+        raise ValueError("sigma (the noise standard deviation in image units, or 'auto' in a session) is required")
     return _abi.OfFuseOpts(_int_in("radius", radius, 1, _abi.FUSE_MAX_RADIUS),
                            _int_in("patch", patch, 0, _abi.FUSE_MAX_PATCH), _number("sigma", sigma, True),
                            _number("strength", strength, True), _number("alpha1", alpha1, False),
@@ -130,16 +137,35 @@ class TemporalDenoiser(DelayedSession):
     effective number of frames averaged in the frame returned last.  One
     denoiser per context: by default the calling thread's context (other
     calls of the package may run between pushes), or a `context`
-    (_native.Context) of your own.  `sigma` is required."""
+    (_native.Context) of your own.
+
+    `sigma` is required: the noise standard deviation in image units, or
+    'auto'.  With 'auto' every frame is fused with a sigma of its own, the
+    root mean square of estimate_noise(frame k, frame k+1, flow, mask) over
+    its adjacent pairs (t-1, t) and (t, t+1) that rest on at least a quarter
+    of the pixels, else estimate_noise(frame t), never below `noise_floor`
+    (0.25 on a 0..255 scale, below the 1/sqrt(12) of 8-bit quantisation: scale
+    it with your value range; of_denoise_open_auto).  `last_sigma` holds the
+    sigma of the frame returned last, in either mode."""
 
     _PREFIX, _NAME = "of_denoise_", "denoiser"
 
     def __init__(self, shape, method='classic+nl-fast', params=None, sigma=None, radius=1, strength=4.0, patch=2,
-                 alpha1=0.01, alpha2=0.5, context=None):
+                 alpha1=0.01, alpha2=0.5, context=None, noise_floor=0.25):
+        self._auto = _is_auto(sigma)
+        self._floor = _number("noise_floor", noise_floor, True)
+        fixed = self._floor if self._auto else sigma  # the automatic session does not read the field
         super().__init__(shape, method, params,
-                         lambda H, W: _fuse_opts(sigma, radius, strength, patch, alpha1, alpha2), context)
+                         lambda H, W: _fuse_opts(fixed, radius, strength, patch, alpha1, alpha2), context)
         self.radius = self._opts.radius
         self.last_weight = None
+        self.last_sigma = None
+
+    def _open(self, ctx, P):
+        if not self._auto:
+            return super()._open(ctx, P)
+        return ctx.lib.of_denoise_open_auto(ctx.handle, C.byref(P), self.H, self.W, self.channels,
+                                            C.byref(self._opts), self._floor)
 
     def _step(self, call, *args):
         out = np.empty(self.shape, dtype=np.float32)
@@ -149,6 +175,9 @@ class TemporalDenoiser(DelayedSession):
         if idx[0] < 0:
             return None
         self.last_weight = wgt.astype(np.float64)
+        sigma = C.c_double(0.0)
+        self._call("last_sigma", C.byref(sigma))
+        self.last_sigma = sigma.value
         return int(idx[0]), out.astype(np.float64)
 
     def push(self, frame):
@@ -162,11 +191,14 @@ class TemporalDenoiser(DelayedSession):
 
 
 def denoise_frames(frames, method='classic+nl-fast', sigma=None, radius=1, strength=4.0, patch=2, alpha1=0.01,
-                   alpha2=0.5, params=None, return_weight=False):
+                   alpha2=0.5, params=None, return_weight=False, noise_floor=0.25, return_sigma=False):
     """Denoise `frames` (a sequence of at least one (H, W) or (H, W, 3) frame
     of one shape) with a TemporalDenoiser: returns (T, H, W[, 3]) float64;
     with `return_weight` also the (T, H, W) float64 effective number of frames
-    averaged per pixel.  `sigma` is required."""
-    out, wgt = TemporalDenoiser.run_clip(frames, "last_weight", method, params, sigma, radius, strength, patch, alpha1,
-                                         alpha2)
-    return (out, wgt) if return_weight else out
+    averaged per pixel, with `return_sigma` also the (T,) float64 sigma every
+    frame was fused with, in that order.  `sigma` is required: a number, or
+    'auto' with its `noise_floor` (TemporalDenoiser)."""
+    out, (wgt, sig) = TemporalDenoiser.run_clip(frames, ("last_weight", "last_sigma"), method, params, sigma, radius,
+                                                strength, patch, alpha1, alpha2, None, noise_floor)
+    res = (out,) + ((wgt,) if return_weight else ()) + ((sig,) if return_sigma else ())
+    return res if len(res) > 1 else out
