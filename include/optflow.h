@@ -529,7 +529,9 @@ int of_track_seed(of_ctx *ctx, const float *gray, int H, int W, const of_track_o
  *                    of_params given at open (out_fw, out_bw, state_fw,
  *                    state_bw, any of which may be NULL, are bitwise those of
  *                    of_estimate_flow_bidir on that pair with alpha1 / alpha2
- *                    of the options; the stats likewise), advances the table
+ *                    of the options; the stats likewise; after
+ *                    of_session_set_flow_scale they are bitwise those of
+ *                    of_estimate_flow_bidir_scaled on that pair), advances the table
  *                    along them on the device, seeds on this frame's gray
  *                    plane with start = this frame's index, and keeps the
  *                    frame as the previous one.  The gray plane is the frame
@@ -632,7 +634,9 @@ int of_fuse_frames(of_ctx *ctx, const float *center, int H, int W, int C, int n,
  *                     k-1 and this one are estimated from a fresh copy of the
  *                     of_params given at open and zero initial flows; flows
  *                     and states are bitwise those of of_estimate_flow_bidir
- *                     on that pair with alpha1 / alpha2 of the options.  For
+ *                     on that pair with alpha1 / alpha2 of the options (of
+ *                     of_estimate_flow_bidir_scaled after
+ *                     of_session_set_flow_scale).  For
  *                     k >= R frame t = k - R is fused and written to out
  *                     (H x W x C) and out_weight (H x W or NULL), and
  *                     *out_index = t; otherwise *out_index = -1 and out is
@@ -858,7 +862,9 @@ int of_warp_affine(of_ctx *ctx, const float *im, int H, int W, int C, const doub
  *   of_stab_push   frame k = 0, 1, ...  For k > 0 both flows between frame k-1
  *                  and this one are estimated from a fresh copy of the
  *                  of_params given at open and zero initial flows (bitwise
- *                  of_estimate_flow_bidir with alpha1 / alpha2 of the options),
+ *                  of_estimate_flow_bidir with alpha1 / alpha2 of the options,
+ *                  or of_estimate_flow_bidir_scaled after
+ *                  of_session_set_flow_scale),
  *                  and M_{k-1} = the matrix of of_fit_motion on the
  *                  device-resident forward flow with the forward state as
  *                  `state`, no weight and `fit` of the options.  A motion
@@ -911,6 +917,99 @@ int of_stab_push(of_ctx *ctx, const float *frame, float *out, uint8_t *out_valid
 int of_stab_flush(of_ctx *ctx, float *out, uint8_t *out_valid, double *out_transform, int32_t *degenerate,
                   int32_t *out_index);
 int of_stab_close(of_ctx *ctx);
+
+/*
+ * Reduced-resolution flow with edge-aware upsampling.  The flow is estimated
+ * on frames reduced by an integer factor and brought back to full size by a
+ * joint bilateral filter guided by the full-resolution frame, so that motion
+ * boundaries land on the picture's edges instead of being smeared over s
+ * pixels as a plain resize (of_resample_flow) would leave them.  Everything in
+ * double from the fp32 inputs, no fma contraction, no transcendental, in
+ * exactly the order written (a numpy float64 restatement gives the same bits).
+ * s = scale, an integer 2..4; hs = ceil(H/s), ws = ceil(W/s).  Images are
+ * H x W x C interleaved, C 1..4; flows planar.  H * W >= 2^31: OF_ENOTSUP.
+ *
+ * of_reduce_frame: the box reduction L (hs x ws x C) of im.
+ *   L_c(a, b) = (float)(S/m)
+ *   S = the sum of I_c(i, j) over rows i = a*s .. min(a*s + s, H) - 1 and,
+ *       inside each row, columns j = b*s .. min(b*s + s, W) - 1, row-major,
+ *       starting from +0.0;  m = the number of terms
+ *
+ * of_flow_upsample: the low flow f (planar 2 x hs x ws, in low-resolution
+ * pixels) with its low guide L (hs x ws x C, the reduction of the frame the
+ * flow starts in) onto the full guide G (H x W x C).  h2 = range*range.  For
+ * output pixel (i, j):
+ *   r = (i - 0.5*(s-1))/s;  q = (j - 0.5*(s-1))/s;  a0 = floor(r);  b0 = floor(q)
+ *   U = V = Sw = 0;  Us = Vs = Ss = 0
+ *   for a = a0-1 .. a0+2, inside that b = b0-1 .. b0+2 (row-major), skipped
+ *   when a or b is outside the low frame or f(a,b).x or .y is not finite:
+ *     wa = max(1 - |a - r|/2, 0);  wb = max(1 - |b - q|/2, 0);  wsp = wa*wb
+ *     D = sum over c ascending: d = G_c(i,j) - L_c(a,b); += d*d
+ *     z = D/(C*h2);  x = z < 1 ? z : 1;  wr = (1 - x)*(1 - x);  w = wsp*wr
+ *     U += w*fx; V += w*fy; Sw += w;   Us += wsp*fx; Vs += wsp*fy; Ss += wsp
+ *   Sw > 0:      out = ((float)(s*(U/Sw)),  (float)(s*(V/Sw))),  info 0
+ *   else Ss > 0: out = ((float)(s*(Us/Ss)), (float)(s*(Vs/Ss))), info 1
+ *   else:        out = (NaN, NaN),                               info 2
+ * info 1: no neighbour looks like this pixel, the spatial weights alone
+ * decide.  A G value that is not finite makes D not finite; x = z < 1 ? z : 1
+ * then gives x = 1 and wr = 0, so such a pixel takes the spatial branch.  A
+ * low flow of +-1e30 is finite and enters the sums as it is.
+ *   f_lo     : planar 2 x hs x ws
+ *   L        : hs x ws x C
+ *   G        : H x W x C
+ *   out_uv   : planar 2 x H x W, in full-resolution pixels
+ *   out_info : H x W bytes, or NULL
+ * Options: any value out of range or not finite: OF_EINVAL, checked on the
+ * host before any launch.  The low size is not an argument: it is hs x ws of
+ * (H, W, scale), and the buffers are taken to have it.
+ */
+typedef struct of_upsample_opts {
+  int32_t scale;   /* s, 2..4 (of_session_set_flow_scale: 1 clears) */
+  int32_t pad_;
+  double range;    /* photometric cutoff in image units, finite, > 0 (20 for 0..255 frames) */
+} of_upsample_opts;
+int of_reduce_frame(of_ctx *ctx, const float *im, int H, int W, int C, int scale, float *out);
+int of_flow_upsample(of_ctx *ctx, const float *f_lo, const float *L, const float *G, int H, int W, int C,
+                     const of_upsample_opts *opts, float *out_uv, uint8_t *out_info);
+/*
+ * The one-call entries: both frames are reduced on the device, the existing
+ * estimate runs unchanged on the reduced pair at hs x ws from zero initial
+ * flows (with params->auto_level the pyramid depth follows from that size),
+ * every low flow is upsampled with its own first frame as guide (frame 1 for
+ * the forward flow, frame 2 for the backward one), and the states are the
+ * forward-backward check of the full-resolution upsampled flows.  The result
+ * is bitwise the composition of the stage entries through the host:
+ *   L1 = of_reduce_frame(im1); L2 = of_reduce_frame(im2)
+ *   f, b = of_estimate_flow_bidir(L1, L2 at hs x ws)      (of_estimate_flow for the one direction)
+ *   out_fw = of_flow_upsample(f, L1, im1); out_bw = of_flow_upsample(b, L2, im2)
+ *   state_fw = of_fb_consistency(out_fw, out_bw); state_bw = (out_bw, out_fw)
+ * C is 1 or 3.  The stats are those of the reduced estimate, with the
+ * reduction charged to preprocess_ms (of stats_fw) and total_ms of stats /
+ * stats_fw the whole call's wall time.  No weight is accepted, as for
+ * of_estimate_flow_bidir.  state_*, stats* may be NULL.
+ */
+int of_estimate_flow_scaled(of_ctx *ctx, of_params *params, const float *im1, const float *im2, int H, int W, int C,
+                            const of_upsample_opts *opts, float *out_uv, of_stats *stats);
+int of_estimate_flow_bidir_scaled(of_ctx *ctx, of_params *params, const float *im1, const float *im2, int H, int W,
+                                  int C, const of_upsample_opts *opts, double alpha1, double alpha2, float *out_fw,
+                                  float *out_bw, uint8_t *state_fw, uint8_t *state_bw, of_stats *stats_fw,
+                                  of_stats *stats_bw);
+/*
+ * of_session_set_flow_scale: the open sessions named by `kinds` (one or more
+ * of OF_SESSION_*) estimate their pairs as of_estimate_flow_bidir_scaled with
+ * `opts` from now on; scale 1 (range is then not read) returns them to
+ * of_estimate_flow_bidir.  Allowed between a session's open and its second
+ * push, that is before its first pair; later, or with a named kind not open,
+ * or kinds naming none: OF_EINVAL, and no session is changed.  What follows
+ * the estimate in a push (advance, fuse, compose, noise, fit, warp) sees
+ * full-resolution flows and states and is unchanged.  The reduced frames and
+ * low flows are arena memory of the push: a session's own allocations, and so
+ * OF_OPT_DEVICE_BYTES of an open session, do not change.
+ */
+#define OF_SESSION_TRACKS 1
+#define OF_SESSION_DENOISE 2
+#define OF_SESSION_STAB 4
+int of_session_set_flow_scale(of_ctx *ctx, int kinds, const of_upsample_opts *opts);
 
 /*
  * Layered motion segmentation.  of_fit_motion finds one motion, the dominant

@@ -17,6 +17,7 @@
 //   kernels_track.hip  point tracker: advance and seed steps
 //   kernels_fuse.hip   temporal denoising: flow composition, frame fusion
 //   kernels_noise.hip  noise-level estimation: the two estimators' keys, the exact radix selection of their median
+//   kernels_upsample.hip reduced-resolution flow: the box reduction of a frame, the edge-aware upsampling of a flow
 //   kernels_motion.hip global motion: the passes of the robust parametric fit, the affine warp
 //   kernels_layers.hip layered motion segmentation (uses the fit's passes)
 //   kernels_solve.hip  what the solvers share (partials, fixed-order sums, residual), norm and residual diagnostics
@@ -32,7 +33,8 @@
 //   host_image.hip  image / flow-field helpers, taps, pyramids, ROF, derivatives, medians
 //   host_solve.hip  CG and SOR dispatch, solve log, deferred statistics, gen_* solvers
 //   host_flow.hip   assembly dispatch, token, per-level IRLS loops, schedule, estimate_*
-//   host_session.hip what the frame-sequence sessions share: lookup and free, open and push prologues, delayed emission
+//   host_upsample.hip reduced-resolution flow: reduction, upsampling, the scaled estimates, stage and one-call entries
+//   host_session.hip what the frame-sequence sessions share: lookup and free, open and push prologues, delayed emission, the flow-scale switch
 //   host_track.hip  point tracker: advance and seed steps, stage entries, the session
 //   host_noise.hip  noise-level estimation: the pair and single-frame estimators, their stage entries
 //   host_fuse.hip   temporal denoising: flow composition, frame fusion, stage entries, the session and its automatic sigma
@@ -63,6 +65,7 @@
 #include "kernels_track.hip"
 #include "kernels_fuse.hip"
 #include "kernels_noise.hip"
+#include "kernels_upsample.hip"
 #include "kernels_motion.hip"
 #include "kernels_layers.hip"
 #include "kernels_solve.hip"
@@ -76,6 +79,7 @@
 #include "host_image.hip"
 #include "host_solve.hip"
 #include "host_flow.hip"
+#include "host_upsample.hip"
 #include "host_session.hip"
 #include "host_track.hip"
 #include "host_noise.hip"

@@ -177,6 +177,7 @@ struct Session {
   std::vector<float *> frame;  // frame k at k % frame.size(): H x W x C dense
   std::vector<void *> owned;   // every device allocation of the session
   size_t bytes = 0;            // of all of them
+  of_upsample_opts up = {1, 0, 0.0};  // of_session_set_flow_scale: scale > 1 estimates the pairs reduced
   virtual ~Session() = default;
   template <typename T>
   T *alloc(size_t count) {

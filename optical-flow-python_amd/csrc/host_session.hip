@@ -1,7 +1,8 @@
 // host_session.hip — what the frame-sequence sessions of a context (point
 // tracker, temporal denoiser, stabiliser: Session, host_core.h) share: the
-// words of their messages, lookup and free, the open and push prologues and
-// the bookkeeping of the delayed emitters.
+// words of their messages, lookup and free, the open and push prologues, the
+// bookkeeping of the delayed emitters and the switch to reduced-resolution
+// pairs (of_session_set_flow_scale).
 namespace {
 
 // the words that differ between the sessions' messages
@@ -79,7 +80,9 @@ void session_not_flushed(const Session *s, int kind) {
 
 // The first half of a push: the caller's frame goes into its ring slot, and
 // when there is a previous frame the pair (previous, this) is estimated in
-// both directions from zero flows.  st_fw / st_bw: dense H x W device bytes
+// both directions from zero flows, at full resolution or, after
+// of_session_set_flow_scale, reduced and upsampled (either way r.fw / r.bw and
+// the states are full-resolution).  st_fw / st_bw: dense H x W device bytes
 // for the forward-backward states, or nullptr; sf / sb: the passes' statistics
 // (zeroed here), or nullptr.  fw.p is nullptr on the first frame.
 struct PushPair {
@@ -98,6 +101,13 @@ PushPair session_push(of_ctx *c, Session *s, const float *frame, double alpha1, 
   if (sb) memset(sb, 0, sizeof(*sb));
   r.wall = WallClock();
   of_params P = s->P;
+  if (s->up.scale > 1) {
+    r.fw = new_f2(c, H, W);
+    r.bw = new_f2(c, H, W);
+    estimate_bidir_scaled_dev(c, &P, s->frame[(k - 1) % nf], r.cur, H, W, C, s->up, r.fw, r.bw, alpha1, alpha2, st_fw,
+                              st_bw, sf, sb);
+    return r;
+  }
   r.fw = init_flow(c, nullptr, H, W);
   r.bw = init_flow(c, nullptr, H, W);
   estimate_bidir_dev(c, &P, s->frame[(k - 1) % nf], r.cur, H, W, C, r.fw, r.bw, alpha1, alpha2, st_fw, st_bw, sf, sb);
@@ -119,3 +129,28 @@ int session_next_emit(Session *s, int R, bool flush) {
 }
 
 }  // namespace
+
+extern "C" {
+
+int of_session_set_flow_scale(of_ctx *c, int kinds, const of_upsample_opts *o) {
+  if (!c) return OF_EINVAL;
+  try {
+    check_upsample_opts(o, true);
+    REQUIRE(kinds > 0 && kinds < (1 << SES_KINDS), OF_EINVAL, "kinds must name one or more of OF_SESSION_*");
+    // every named session is checked before any is changed
+    for (int kind = 0; kind < SES_KINDS; ++kind) {
+      if (!(kinds >> kind & 1)) continue;
+      const Session *s = c->session[kind];
+      REQUIRE(s, OF_EINVAL, session_not_open(kind));
+      REQUIRE(s->frames < 2 && !s->flushed, OF_EINVAL,
+              std::string("the ") + SESSION_KIND[kind].name +
+                  " has estimated a pair already (set the flow scale before the second push)");
+    }
+    for (int kind = 0; kind < SES_KINDS; ++kind)
+      if (kinds >> kind & 1) c->session[kind]->up = o->scale == 1 ? of_upsample_opts{1, 0, 0.0} : *o;
+    return OF_OK;
+  }
+  API_CATCH(c)
+}
+
+}  // extern "C"

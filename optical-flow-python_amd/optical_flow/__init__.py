@@ -13,6 +13,7 @@ from optical_flow.temporal import compose_flows, fuse_frames, TemporalDenoiser, 
 from optical_flow.noise import estimate_noise, NoiseEstimate
 from optical_flow.motion import (fit_motion, warp_affine, Stabilizer, stabilize_frames, MotionFit, segment_motion,
                                  MotionLayers, MotionLayer, LAYER_NONE)
+from optical_flow.upsample import reduce_frame, upsample_flow
 from optical_flow.utils.warping import warp_image
 from optical_flow.utils.occlusion import forward_backward_check, FB_CONSISTENT, FB_OCCLUDED, FB_OUT_OF_FRAME
 from optical_flow.io.flo_io import read_flo, write_flo
@@ -28,4 +29,5 @@ __all__ = ['estimate_flow', 'estimate_flow_batch', 'PairStream', 'read_flo', 'wr
            'seed_points', 'PointTracker', 'track_points', 'Trajectories', 'TRACK_ALIVE', 'TRACK_OCCLUDED',
            'TRACK_LEFT_FRAME', 'TRACK_MOTION_BOUNDARY', 'compose_flows', 'fuse_frames', 'TemporalDenoiser',
            'denoise_frames', 'fit_motion', 'warp_affine', 'Stabilizer', 'stabilize_frames', 'MotionFit',
-           'segment_motion', 'MotionLayers', 'MotionLayer', 'LAYER_NONE', 'estimate_noise', 'NoiseEstimate']
+           'segment_motion', 'MotionLayers', 'MotionLayer', 'LAYER_NONE', 'estimate_noise', 'NoiseEstimate',
+           'reduce_frame', 'upsample_flow']

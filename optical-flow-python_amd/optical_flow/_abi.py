@@ -189,6 +189,16 @@ class OfMotionLayer(C.Structure):
                 ("pixels", C.c_int64), ("degenerate", C.c_int32), ("pad_", C.c_int32)]
 
 
+# reduced-resolution flow (include/optflow.h, "Reduced-resolution flow with edge-aware upsampling")
+UPSAMPLE_MIN_SCALE, UPSAMPLE_MAX_SCALE = 2, 4
+UPSAMPLE_MAX_CHANNELS = 4
+OF_SESSION_TRACKS, OF_SESSION_DENOISE, OF_SESSION_STAB = 1, 2, 4  # of_session_set_flow_scale
+
+
+class OfUpsampleOpts(C.Structure):
+    _fields_ = [("scale", C.c_int32), ("pad_", C.c_int32), ("range", C.c_double)]
+
+
 def penalty(kind, p0=1.0, p1=0.0):
     return OfPenalty(PENALTY[kind], 0, float(p0), float(p1))
 

@@ -11,7 +11,8 @@ import threading
 import numpy as np
 
 from optical_flow._abi import (OfParams, OfStats, OfCgGeometry, OfSolveRecord, OfProgressFn, OfTrackOpts, OfFuseOpts,
-                               OfNoiseEstimate, OfMotionOpts, OfMotionFit, OfStabOpts, OfLayersOpts, OfMotionLayer, OF_ABI_VERSION,
+                               OfNoiseEstimate, OfMotionOpts, OfMotionFit, OfStabOpts, OfLayersOpts, OfMotionLayer,
+                               OfUpsampleOpts, OF_ABI_VERSION,
                                OF_EINVAL, OF_ENOTSUP)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -91,6 +92,15 @@ _SIGS = {
     "of_stab_push": ([_vp, _fp, _fp, _u8p, _dp, _dp, _i32p, _i32p], C.c_int),
     "of_stab_flush": ([_vp, _fp, _u8p, _dp, _i32p, _i32p], C.c_int),
     "of_stab_close": ([_vp], C.c_int),
+    "of_reduce_frame": ([_vp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp], C.c_int),
+    "of_flow_upsample": ([_vp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.POINTER(OfUpsampleOpts), _fp, _u8p],
+                         C.c_int),
+    "of_estimate_flow_scaled": ([_vp, C.POINTER(OfParams), _fp, _fp, C.c_int, C.c_int, C.c_int,
+                                 C.POINTER(OfUpsampleOpts), _fp, C.POINTER(OfStats)], C.c_int),
+    "of_estimate_flow_bidir_scaled": ([_vp, C.POINTER(OfParams), _fp, _fp, C.c_int, C.c_int, C.c_int,
+                                       C.POINTER(OfUpsampleOpts), C.c_double, C.c_double, _fp, _fp, _u8p, _u8p,
+                                       C.POINTER(OfStats), C.POINTER(OfStats)], C.c_int),
+    "of_session_set_flow_scale": ([_vp, C.c_int, C.POINTER(OfUpsampleOpts)], C.c_int),
     "of_segment_motion": ([_vp, _fp, C.c_int, C.c_int, _fp, _u8p, C.POINTER(OfLayersOpts), C.POINTER(OfMotionLayer),
                            _i32p, _u8p, _u8p], C.c_int),
     "of_compute_flow_base": ([_vp, C.POINTER(OfParams), _fp, C.c_int, C.c_int, C.c_int, _fp, C.c_int,

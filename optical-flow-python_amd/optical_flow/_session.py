@@ -6,6 +6,7 @@ import ctypes as C
 
 import numpy as np
 
+from optical_flow import _abi
 from optical_flow import _native as nat
 from optical_flow.methods.config import load_of_method
 
@@ -30,6 +31,14 @@ def _number(name, v, positive):
             or (v <= 0 if positive else v < 0):
         raise ValueError(f"{name} must be a finite number {'> 0' if positive else '>= 0'}, got {v!r}")
     return float(v)
+
+
+def _flow_scale(scale, upsample_range, range_name="upsample_range"):
+    """The `scale` / `upsample_range` keywords as an of_upsample_opts, or None
+    for scale 1 (the full-resolution estimate, today's C calls)."""
+    scale = _int_in("scale", scale, 1, _abi.UPSAMPLE_MAX_SCALE)
+    rng = _number(range_name, upsample_range, True)
+    return None if scale == 1 else _abi.OfUpsampleOpts(scale, 0, rng)
 
 
 def _frame_size(H, W):
@@ -97,21 +106,31 @@ class Closing:
 class Session(Closing):
     """A frame-sequence session of a context: of_<kind>_open at construction,
     of_<kind>_close in close().  Subclasses name the C entries' prefix
-    (_PREFIX) and themselves in the "is closed" error (_NAME)."""
-    _PREFIX = _NAME = None
+    (_PREFIX), their OF_SESSION_* bit (_KIND) and themselves in the "is closed"
+    error (_NAME)."""
+    _PREFIX = _NAME = _KIND = None
 
-    def __init__(self, shape, method, params, make_opts, context):
+    def __init__(self, shape, method, params, make_opts, context, scale=1, upsample_range=20.0):
         """`make_opts(H, W)` validates the session's own arguments into its
         options struct; everything is validated before the library or a
-        context is touched."""
+        context is touched.  `scale` > 1 estimates every pair at reduced
+        resolution (of_session_set_flow_scale right after the open); 1 makes
+        no such call."""
         self._ctx = None
         self.shape, self.H, self.W, self.channels = _frame_shape(shape)
         self._opts = make_opts(self.H, self.W)
+        up = _flow_scale(scale, upsample_range)
         P = method_params(method, params)[1]
         self.frames = 0
         ctx = nat.context() if context is None else context
         ctx.check(self._open(ctx, P))
         self._ctx = ctx
+        if up is not None:
+            try:
+                ctx.check(ctx.lib.of_session_set_flow_scale(ctx.handle, self._KIND, C.byref(up)))
+            except Exception:
+                self.close()
+                raise
 
     def _open(self, ctx, P):
         """The return code of the session's open entry on `ctx`."""

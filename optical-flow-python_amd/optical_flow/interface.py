@@ -11,10 +11,11 @@ import numpy as np
 from optical_flow import _abi
 from optical_flow import _native as nat
 from optical_flow.methods.base import progress_printer
-from optical_flow._session import Closing, method_params
+from optical_flow._session import Closing, _flow_scale, method_params
 
 
-def estimate_flow(im1, im2, method='classic+nl-fast', params=None, gt=None, data_weight=None):
+def estimate_flow(im1, im2, method='classic+nl-fast', params=None, gt=None, data_weight=None, scale=1,
+                  upsample_range=20.0):
     """Flow (H, W, 2) float64 from im1 to im2; (H, W) or (H, W, >=3) inputs.
     Prints what the reference's compute_flow prints.  `gt` (an extension:
     the reference's estimate_flow has no such argument) is handed to the
@@ -32,12 +33,24 @@ def estimate_flow(im1, im2, method='classic+nl-fast', params=None, gt=None, data
     fill them with plausible values rather than extremes.  None is the
     unweighted flow, bitwise.  A wrong shape or a NaN, Inf or negative value
     raises ValueError; a general spatial_filters list or 'classic-c-a' with a
-    weight raises NotImplementedError."""
+    weight raises NotImplementedError.
+
+    `scale` (an extension too) = 2..4 trades accuracy for speed: both frames
+    are reduced by that integer factor (reduce_frame), the flow is estimated
+    on the reduced pair, whose pyramid is as many levels shorter, and brought
+    back to full size along im1's edges (upsample_flow with `upsample_range`
+    as its `range`: on the frames' value scale, 20 for 0..255), all in one C
+    call (of_estimate_flow_scaled).  1 is the full-resolution estimate, the
+    same C call as without the keyword.  (H, W) and (H, W, >=3) frames only,
+    and not together with `data_weight`: NotImplementedError."""
+    up = _flow_scale(scale, upsample_range)
     im1 = np.asarray(im1, dtype=float)
     im2 = np.asarray(im2, dtype=float)
     ope, P = method_params(method, params)
     H, W = im1.shape[:2]
     wgt = nat.data_weight(data_weight, H, W)
+    if up is not None and (wgt is not None or (im1.ndim == 3 and im1.shape[2] < 3)):
+        raise NotImplementedError("scale > 1 takes (H, W) or (H, W, >=3) frames and no data_weight")
     if im1.ndim == 3 and im1.shape[2] < 3:
         # interface.py:47: channels are concatenated, no colour conversion
         ope.images = np.concatenate([im1, im2], axis=2)
@@ -55,8 +68,12 @@ def estimate_flow(im1, im2, method='classic+nl-fast', params=None, gt=None, data
     ctx = nat.context()
     fn, flags = progress_printer(ope, gt)  # the reference's compute_flow prints (interface.py:66)
     with ctx.progress(fn, flags):
-        ctx.check(ctx.lib.of_estimate_flow_weighted(ctx.handle, C.byref(P), nat.ptr(a), nat.ptr(b), H, W, Cc, None,
-                                                    nat.ptr(wgt), nat.ptr(out), C.byref(st)))
+        if up is None:
+            ctx.check(ctx.lib.of_estimate_flow_weighted(ctx.handle, C.byref(P), nat.ptr(a), nat.ptr(b), H, W, Cc, None,
+                                                        nat.ptr(wgt), nat.ptr(out), C.byref(st)))
+        else:
+            ctx.check(ctx.lib.of_estimate_flow_scaled(ctx.handle, C.byref(P), nat.ptr(a), nat.ptr(b), H, W, Cc,
+                                                      C.byref(up), nat.ptr(out), C.byref(st)))
     ope.alpha = P.alpha
     ope.last_stats = st.as_dict()
     return nat.interleaved(out)
@@ -64,7 +81,8 @@ def estimate_flow(im1, im2, method='classic+nl-fast', params=None, gt=None, data
 BidirectionalFlow = namedtuple('BidirectionalFlow', ['forward', 'backward', 'occ_forward', 'occ_backward'])
 
 
-def estimate_flow_bidirectional(im1, im2, method='classic+nl-fast', params=None, alpha1=0.01, alpha2=0.5):
+def estimate_flow_bidirectional(im1, im2, method='classic+nl-fast', params=None, alpha1=0.01, alpha2=0.5, scale=1,
+                                upsample_range=20.0):
     """Flow im1 -> im2, flow im2 -> im1 and where each can be trusted.
 
     Returns BidirectionalFlow(forward, backward, occ_forward, occ_backward):
@@ -74,12 +92,22 @@ def estimate_flow_bidirectional(im1, im2, method='classic+nl-fast', params=None,
     and the same with the flows exchanged (utils/occlusion.py: FB_CONSISTENT,
     FB_OCCLUDED, FB_OUT_OF_FRAME).  (H, W) and (H, W, >=3) frames take one C
     call (of_estimate_flow_bidir) that runs the gray conversion, the
-    structure-texture split and the image pyramids once for both directions."""
+    structure-texture split and the image pyramids once for both directions.
+
+    `scale` = 2..4 estimates both flows on the frames reduced by that factor
+    and upsamples each along its own first frame (im1 for forward, im2 for
+    backward; `upsample_range` as upsample_flow's `range`); the masks are the
+    check of the full-resolution flows (of_estimate_flow_bidir_scaled, one C
+    call; see estimate_flow).  1 is the full-resolution estimate, the same C
+    call as without the keyword."""
+    up = _flow_scale(scale, upsample_range)
     im1 = np.asarray(im1, dtype=float)
     im2 = np.asarray(im2, dtype=float)
     if im1.shape != im2.shape or im1.ndim not in (2, 3):
         raise ValueError(f"frames must share one (H, W) or (H, W, C) shape, got {im1.shape} / {im2.shape}")
     H, W = im1.shape[:2]
+    if up is not None and im1.ndim == 3 and im1.shape[2] < 3:
+        raise NotImplementedError("scale > 1 takes (H, W) or (H, W, >=3) frames")
     if im1.ndim == 3 and im1.shape[2] < 3:
         # estimate_flow's compute_flow route (interface.py:47), once per direction
         from optical_flow.utils.occlusion import forward_backward_check
@@ -100,9 +128,16 @@ def estimate_flow_bidirectional(im1, im2, method='classic+nl-fast', params=None,
     ctx = nat.context()
     fn, flags = progress_printer(ope, None)
     with ctx.progress(fn, flags):
-        ctx.check(ctx.lib.of_estimate_flow_bidir(ctx.handle, C.byref(P), nat.ptr(a), nat.ptr(b), H, W, Cc, None, None,
-                                                 nat.ptr(out_f), nat.ptr(out_b), float(alpha1), float(alpha2),
-                                                 nat.u8ptr(occ_f), nat.u8ptr(occ_b), C.byref(st_f), C.byref(st_b)))
+        if up is None:
+            ctx.check(ctx.lib.of_estimate_flow_bidir(ctx.handle, C.byref(P), nat.ptr(a), nat.ptr(b), H, W, Cc, None,
+                                                     None, nat.ptr(out_f), nat.ptr(out_b), float(alpha1),
+                                                     float(alpha2), nat.u8ptr(occ_f), nat.u8ptr(occ_b),
+                                                     C.byref(st_f), C.byref(st_b)))
+        else:
+            ctx.check(ctx.lib.of_estimate_flow_bidir_scaled(ctx.handle, C.byref(P), nat.ptr(a), nat.ptr(b), H, W, Cc,
+                                                            C.byref(up), float(alpha1), float(alpha2),
+                                                            nat.ptr(out_f), nat.ptr(out_b), nat.u8ptr(occ_f),
+                                                            nat.u8ptr(occ_b), C.byref(st_f), C.byref(st_b)))
     return BidirectionalFlow(nat.interleaved(out_f), nat.interleaved(out_b), occ_f, occ_b)
 
 
@@ -115,7 +150,7 @@ INTERP_FILLED = 4
 
 
 def interpolate_frames(im1, im2, t=0.5, method='classic+nl-fast', params=None, flows=None, alpha1=0.01, alpha2=0.5,
-                       return_info=False):
+                       return_info=False, scale=1, upsample_range=20.0):
     """The frame(s) at time(s) `t`, strictly between im1 (t = 0) and im2
     (t = 1), by occlusion-aware interpolation along the flows of both
     directions (Baker et al. 2011 sec. 3.3.2; include/optflow.h states the
@@ -135,7 +170,14 @@ def interpolate_frames(im1, im2, t=0.5, method='classic+nl-fast', params=None, f
     motion at time t, (H, W, 2) float64, and the (H, W) uint8 info byte
     (INTERP_BLEND, INTERP_FRAME1_ONLY, INTERP_FRAME2_ONLY or INTERP_NEITHER,
     plus INTERP_FILLED where the motion came from hole filling); estimated
-    flows then make the round trip of estimate_flow_bidirectional."""
+    flows then make the round trip of estimate_flow_bidirectional.
+
+    `scale` / `upsample_range` apply where the flows are estimated, as in
+    estimate_flow_bidirectional, whose round trip the flows then make; with
+    `flows` given a `scale` other than 1 is a ValueError."""
+    up = _flow_scale(scale, upsample_range)
+    if up is not None and flows is not None:
+        raise ValueError("scale applies to estimated flows only: leave it at 1 when `flows` is given")
     im1 = np.asarray(im1, dtype=float)
     im2 = np.asarray(im2, dtype=float)
     if im1.shape != im2.shape or im1.ndim not in (2, 3) or im1.size == 0:
@@ -155,14 +197,14 @@ def interpolate_frames(im1, im2, t=0.5, method='classic+nl-fast', params=None, f
         fw, bw = np.asarray(fw), np.asarray(bw)
         if fw.shape != (H, W, 2) or bw.shape != (H, W, 2):
             raise ValueError(f"flows must both be ({H}, {W}, 2), got {fw.shape} / {bw.shape}")
-    elif return_info or (im1.ndim == 3 and Cc != 3):
-        r = estimate_flow_bidirectional(im1, im2, method, params, alpha1, alpha2)
+    elif return_info or (im1.ndim == 3 and Cc != 3) or up is not None:
+        r = estimate_flow_bidirectional(im1, im2, method, params, alpha1, alpha2, scale, upsample_range)
         fw, bw = r.forward, r.backward
     a, b = nat.f32(im1), nat.f32(im2)
     out = np.empty((n, H, W, Cc), dtype=np.float32)
     ut = np.empty((n, 2, H, W), dtype=np.float32) if return_info else None
     info = np.empty((n, H, W), dtype=np.uint8) if return_info else None
-    if flows is not None or return_info or (im1.ndim == 3 and Cc != 3):
+    if flows is not None or return_info or (im1.ndim == 3 and Cc != 3) or up is not None:
         ctx = nat.context()
         ctx.check(ctx.lib.of_interp_frames(ctx.handle, nat.ptr(a), nat.ptr(b), H, W, Cc, nat.ptr(nat.planar(fw)),
                                            nat.ptr(nat.planar(bw)), float(alpha1), float(alpha2), n, nat.dptr(ts),

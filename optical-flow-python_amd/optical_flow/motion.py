@@ -180,16 +180,23 @@ class Stabilizer(DelayedSession):
     could not be inverted and the identity took its place).  One stabiliser per
     context: by default the calling thread's context (other calls of the
     package may run between pushes), or a `context` (_native.Context) of your
-    own."""
+    own.
 
-    _PREFIX, _NAME = "of_stab_", "stabiliser"
+    `scale` = 2..4 estimates every pair's flows at 1/scale of the resolution
+    and brings them back along the frames' edges, as estimate_flow_bidirectional
+    with the same `scale` / `upsample_range` does (of_session_set_flow_scale);
+    the fit and the warp stay at full resolution.  1 is the full-resolution
+    stabiliser."""
+
+    _PREFIX, _NAME, _KIND = "of_stab_", "stabiliser", _abi.OF_SESSION_STAB
 
     def __init__(self, shape, method='classic+nl-fast', params=None, model='similarity', radius=8, sigma_t=3.0,
-                 iters=10, kappa=2.0, decay=0.5, c_min=0.5, alpha1=0.01, alpha2=0.5, context=None):
+                 iters=10, kappa=2.0, decay=0.5, c_min=0.5, alpha1=0.01, alpha2=0.5, context=None, scale=1,
+                 upsample_range=20.0):
         super().__init__(shape, method, params, lambda H, W: _abi.OfStabOpts(
             _motion_opts(model, iters, kappa, decay, c_min), _int_in("radius", radius, 1, _abi.STAB_MAX_RADIUS), 0,
             _number("sigma_t", sigma_t, True), _number("alpha1", alpha1, False), _number("alpha2", alpha2, False)),
-            context)
+            context, scale, upsample_range)
         self.radius = self._opts.radius
         self.last_motion = self.last_transform = self.last_valid = None
         self.last_degenerate = 0
@@ -222,11 +229,13 @@ class Stabilizer(DelayedSession):
 
 
 def stabilize_frames(frames, method='classic+nl-fast', model='similarity', radius=8, sigma_t=3.0, params=None,
-                     iters=10, kappa=2.0, decay=0.5, c_min=0.5, alpha1=0.01, alpha2=0.5, return_transforms=False):
+                     iters=10, kappa=2.0, decay=0.5, c_min=0.5, alpha1=0.01, alpha2=0.5, return_transforms=False,
+                     scale=1, upsample_range=20.0):
     """Stabilise `frames` (a sequence of at least one (H, W) or (H, W, 3)
     frame of one shape) with a Stabilizer: returns (T, H, W[, 3]) float64; with
     `return_transforms` also the (T, 2, 3) float64 S_t each frame was moved
-    by (a point of frame t lies at S_t^-1 of it in the output)."""
+    by (a point of frame t lies at S_t^-1 of it in the output).  `scale` /
+    `upsample_range` estimate the flows at reduced resolution (Stabilizer)."""
     out, tr = Stabilizer.run_clip(frames, "last_transform", method, params, model, radius, sigma_t, iters, kappa,
-                                  decay, c_min, alpha1, alpha2)
+                                  decay, c_min, alpha1, alpha2, None, scale, upsample_range)
     return (out, tr) if return_transforms else out

@@ -146,17 +146,23 @@ class TemporalDenoiser(DelayedSession):
     of the pixels, else estimate_noise(frame t), never below `noise_floor`
     (0.25 on a 0..255 scale, below the 1/sqrt(12) of 8-bit quantisation: scale
     it with your value range; of_denoise_open_auto).  `last_sigma` holds the
-    sigma of the frame returned last, in either mode."""
+    sigma of the frame returned last, in either mode.
 
-    _PREFIX, _NAME = "of_denoise_", "denoiser"
+    `scale` = 2..4 estimates every pair's flows at 1/scale of the resolution
+    and brings them back along the frames' edges, as estimate_flow_bidirectional
+    with the same `scale` / `upsample_range` does (of_session_set_flow_scale);
+    the fusion stays at full resolution.  1 is the full-resolution denoiser."""
+
+    _PREFIX, _NAME, _KIND = "of_denoise_", "denoiser", _abi.OF_SESSION_DENOISE
 
     def __init__(self, shape, method='classic+nl-fast', params=None, sigma=None, radius=1, strength=4.0, patch=2,
-                 alpha1=0.01, alpha2=0.5, context=None, noise_floor=0.25):
+                 alpha1=0.01, alpha2=0.5, context=None, noise_floor=0.25, scale=1, upsample_range=20.0):
         self._auto = _is_auto(sigma)
         self._floor = _number("noise_floor", noise_floor, True)
         fixed = self._floor if self._auto else sigma  # the automatic session does not read the field
         super().__init__(shape, method, params,
-                         lambda H, W: _fuse_opts(fixed, radius, strength, patch, alpha1, alpha2), context)
+                         lambda H, W: _fuse_opts(fixed, radius, strength, patch, alpha1, alpha2), context, scale,
+                         upsample_range)
         self.radius = self._opts.radius
         self.last_weight = None
         self.last_sigma = None
@@ -191,14 +197,17 @@ class TemporalDenoiser(DelayedSession):
 
 
 def denoise_frames(frames, method='classic+nl-fast', sigma=None, radius=1, strength=4.0, patch=2, alpha1=0.01,
-                   alpha2=0.5, params=None, return_weight=False, noise_floor=0.25, return_sigma=False):
+                   alpha2=0.5, params=None, return_weight=False, noise_floor=0.25, return_sigma=False, scale=1,
+                   upsample_range=20.0):
     """Denoise `frames` (a sequence of at least one (H, W) or (H, W, 3) frame
     of one shape) with a TemporalDenoiser: returns (T, H, W[, 3]) float64;
     with `return_weight` also the (T, H, W) float64 effective number of frames
     averaged per pixel, with `return_sigma` also the (T,) float64 sigma every
     frame was fused with, in that order.  `sigma` is required: a number, or
-    'auto' with its `noise_floor` (TemporalDenoiser)."""
+    'auto' with its `noise_floor`; `scale` / `upsample_range` estimate the
+    flows at reduced resolution (TemporalDenoiser)."""
     out, (wgt, sig) = TemporalDenoiser.run_clip(frames, ("last_weight", "last_sigma"), method, params, sigma, radius,
-                                                strength, patch, alpha1, alpha2, None, noise_floor)
+                                                strength, patch, alpha1, alpha2, None, noise_floor, scale,
+                                                upsample_range)
     res = (out,) + ((wgt,) if return_weight else ()) + ((sig,) if return_sigma else ())
     return res if len(res) > 1 else out

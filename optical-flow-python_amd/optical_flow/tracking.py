@@ -150,15 +150,21 @@ class PointTracker(Session):
     in the table and never changes; ended tracks keep their row.  One tracker
     per context: by default the calling thread's context (other calls of the
     package may run between pushes), or a `context` (_native.Context) of
-    your own for a second tracker at the same time."""
+    your own for a second tracker at the same time.
 
-    _PREFIX, _NAME = "of_tracks_", "tracker"
+    `scale` = 2..4 estimates every pair's flows at 1/scale of the resolution
+    and brings them back along the frames' edges, as estimate_flow_bidirectional
+    with the same `scale` / `upsample_range` does (of_session_set_flow_scale);
+    the table and everything else stay at full resolution.  1 is the
+    full-resolution tracker."""
+
+    _PREFIX, _NAME, _KIND = "of_tracks_", "tracker", _abi.OF_SESSION_TRACKS
 
     def __init__(self, shape, method='classic+nl-fast', params=None, step=8, max_tracks=None, min_eig=25.0,
-                 alpha1=0.01, alpha2=0.5, beta1=0.01, beta2=0.002, context=None):
+                 alpha1=0.01, alpha2=0.5, beta1=0.01, beta2=0.002, context=None, scale=1, upsample_range=20.0):
         super().__init__(shape, method, params,
                          lambda H, W: _track_opts(H, W, step, max_tracks, alpha1, alpha2, beta1, beta2, min_eig),
-                         context)
+                         context, scale, upsample_range)
 
     def push(self, frame, return_flows=False):
         """The next frame.  Returns a TrackSnapshot: xy (N, 2) float32, status
@@ -218,11 +224,12 @@ class Trajectories:
 
 
 def track_points(frames, method='classic+nl-fast', params=None, step=8, max_tracks=None, min_eig=25.0, alpha1=0.01,
-                 alpha2=0.5, beta1=0.01, beta2=0.002):
+                 alpha2=0.5, beta1=0.01, beta2=0.002, scale=1, upsample_range=20.0):
     """Track points through `frames` (a sequence of at least one (H, W) or
-    (H, W, 3) frame of one shape) with a PointTracker; returns Trajectories."""
+    (H, W, 3) frame of one shape) with a PointTracker; returns Trajectories.
+    `scale` / `upsample_range` as PointTracker."""
     frames = _clip(frames)
     with PointTracker(frames[0].shape, method, params, step, max_tracks, min_eig, alpha1, alpha2, beta1,
-                      beta2) as tr:
+                      beta2, None, scale, upsample_range) as tr:
         snaps = [tr.push(f) for f in frames]
     return Trajectories.from_snapshots(snaps)
