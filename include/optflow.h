@@ -192,8 +192,9 @@ int of_set_option(of_ctx *ctx, int option, int value);
  *                         grow-only buffers (arena, SOR sweep ring, gather
  *                         buffer): flat across repeated pairs of one size; plus
  *                         an open point tracker's (of_tracks_open) and an open
- *                         temporal denoiser's (of_denoise_open) and an open
- *                         stabiliser's (of_stab_open) buffers, which leave the
+ *                         temporal denoiser's (of_denoise_open), an open
+ *                         stabiliser's (of_stab_open) and an open
+ *                         super-resolver's (of_sr_open) buffers, which leave the
  *                         count again at their close */
 #define OF_OPT_DEVICE_BYTES 4
 /*   OF_OPT_RCCL_NRANKS    ranks of the context's RCCL communicator as RCCL
@@ -625,6 +626,14 @@ int of_fuse_frames(of_ctx *ctx, const float *center, int H, int W, int C, int n,
                    const float *flows, const uint8_t *states, const of_fuse_opts *opts,
                    float *out, float *out_weight);
 /*
+ * of_fuse_weights: the neighbour weights of of_fuse_frames on their own, same
+ * arguments, checks and order:  out_w[k](i,j) = (float)w_k, 0 where
+ * !vis_k(i,j).
+ *   out_w : n x H x W
+ */
+int of_fuse_weights(of_ctx *ctx, const float *center, int H, int W, int C, int n, const float *neigh,
+                    const float *flows, const uint8_t *states, const of_fuse_opts *opts, float *out_w);
+/*
  * The denoiser session: one per context; the last 2R+1 frames (R = radius)
  * and the last 2R adjacent pairs' flows and states stay on the device.
  *   of_denoise_open   frames of H x W x C (C 1 or 3) with the given parameter
@@ -1010,6 +1019,95 @@ int of_estimate_flow_bidir_scaled(of_ctx *ctx, of_params *params, const float *i
 #define OF_SESSION_DENOISE 2
 #define OF_SESSION_STAB 4
 int of_session_set_flow_scale(of_ctx *ctx, int kinds, const of_upsample_opts *opts);
+
+/*
+ * Multi-frame super-resolution along the flow.  The temporal denoiser puts
+ * every warped neighbour back on the frame's own pixel grid; here the frame
+ * and its neighbours are resampled onto a grid s times finer, every
+ * neighbour's pixels placed where its flow says they belong, so the sub-pixel
+ * phases the flows carry add detail instead of being averaged away.  It is the
+ * inverse of the camera model of_reduce_frame states (box integration by an
+ * integer factor).  Everything in double from the fp32 inputs, no fma
+ * contraction, no transcendental, in exactly the order written (a numpy
+ * float64 restatement gives the same bits); bil, inside and near as defined
+ * above ("Using a flow on an image"); images H x W x C interleaved, flows
+ * planar 2 x H x W in low-resolution pixels running centre -> neighbour k,
+ * states as for of_fuse_frames.  C is 1..4, n is 0..8 (with n = 0 neigh, flows
+ * and states may be NULL).  s = factor; the output is sH x sW x C.
+ * s*s*H*W >= 2^31: OF_ENOTSUP.
+ *
+ * Weights:  Wk = of_fuse_weights(center, neigh, flows, states; sigma,
+ * strength, patch), n x H x W fp32 planes.
+ *
+ * Resampling:  rho2 = reach*reach.  For output pixel (Y, X):
+ *   r = (Y - 0.5*(s-1))/s;  q = (X - 0.5*(s-1))/s          (of_flow_upsample's mapping)
+ *   ic = Y / s; jc = X / s                                  (integer division)
+ *   acc_c = 0 for every c;  S = 0
+ *   frames k = 0 (the centre: zr = r, zq = q, R = 1.0), then k = 1..n ascending:
+ *     k >= 1:  R = Wk[k][ic][jc];  R == 0: skip the frame
+ *              u = bil(F_k.x, r, q); v = bil(F_k.y, r, q);  zr = r + v; zq = q + u
+ *              !inside(zr, zq): skip the frame              (a non-finite flow at any tap lands here)
+ *     a0 = floor(zr + 0.5); b0 = floor(zq + 0.5)
+ *     a = a0-1 .. a0+1, inside that b = b0-1 .. b0+1 (row-major), positions outside the frame skipped:
+ *       dy = a - zr; dx = b - zq; x = (dy*dy + dx*dx)/rho2;  !(x < 1): skip the tap
+ *       K = (1 - x)*(1 - x);  w = K*R
+ *       acc_c = acc_c + w*N_k,c[a][b] for every c (ascending);  S = S + w
+ *   out_c = (float)(acc_c/S);  out_support = (float)S
+ * S > 0 always: the centre's nearest tap is closer than 0.5 per axis, so
+ * x < 0.5/0.5625 there.  The 3 x 3 window is complete because reach <= 1.5.
+ * The skips are part of the definition: a zero term must not touch the sign of
+ * a zero sum.  out_support is the weight the output pixel rests on; above the
+ * value of the n = 0 result it counts what the neighbours added.
+ *
+ * Back-projection, one step when back > 0:
+ *   L = of_reduce_frame(out, s)                             (H x W x C again)
+ *   e_c(i,j) = I_c(i,j) - L_c(i,j)
+ *   out_c(Y,X) = (float)(out_c(Y,X) + back*e_c(Y/s, X/s))
+ * With back = 1 the result reduces back to the centre frame, up to rounding;
+ * the centre's noise comes back with it, so the default is 0.
+ *
+ * Two limits.  sigma must cover the aliasing between the frames as well as the
+ * noise: on a strongly aliased scene of the numpy prototype sigma = 5 left a
+ * mean neighbour weight of 0.005, and the output was the single-frame result.
+ * reach = 0.75 is the best of {0.6, 0.75, 1.0, 1.5} in that prototype on one
+ * texture; it is not a measured optimum.
+ *   neigh       : n x H x W x C
+ *   flows       : n x 2 x H x W
+ *   states      : n x H x W bytes, or NULL
+ *   out         : sH x sW x C
+ *   out_support : sH x sW, or NULL
+ * Options: any value out of range or not finite: OF_EINVAL, checked on the
+ * host before any launch (every entry checks the whole struct).
+ */
+typedef struct of_sr_opts {
+  int32_t factor;   /* s, 2..4 */
+  int32_t radius;   /* session only: neighbours on each side, 1..2 */
+  int32_t patch;    /* as of_fuse_opts, 0..3 */
+  int32_t pad_;
+  double sigma, strength;   /* as of_fuse_opts: the neighbour weight */
+  double reach;     /* kernel radius in low-resolution pixels, 0.75..1.5 */
+  double back;      /* back-projection step, 0..1 */
+  double alpha1, alpha2;    /* session only: forward-backward test, as of_fb_consistency; >= 0 */
+} of_sr_opts;
+int of_super_resolve(of_ctx *ctx, const float *center, int H, int W, int C, int n, const float *neigh,
+                     const float *flows, const uint8_t *states, const of_sr_opts *opts, float *out,
+                     float *out_support);
+/*
+ * The super-resolver session: one per context, beside the other kinds; it
+ * keeps what the denoiser session keeps (the last 2R+1 frames, the last 2R
+ * adjacent pairs' flows and states) and of_sr_open / _push / _flush / _close
+ * behave as of_denoise_open / _push / _flush / _close do, with the same
+ * neighbours in the same order (-1, +1, -2, +2; two frames apart through
+ * of_flow_compose).  Frame t is emitted as of_super_resolve of that frame with
+ * those neighbours: out is sH x sW x C, out_support sH x sW or NULL; a clip of
+ * one frame gives the n = 0 result.  The session's buffers count in
+ * OF_OPT_DEVICE_BYTES from open to close.  It is not a kind
+ * of_session_set_flow_scale takes: its pairs are estimated at full resolution.
+ */
+int of_sr_open(of_ctx *ctx, const of_params *params, int H, int W, int C, const of_sr_opts *opts);
+int of_sr_push(of_ctx *ctx, const float *frame, float *out, float *out_support, int32_t *out_index);
+int of_sr_flush(of_ctx *ctx, float *out, float *out_support, int32_t *out_index);
+int of_sr_close(of_ctx *ctx);
 
 /*
  * Layered motion segmentation.  of_fit_motion finds one motion, the dominant

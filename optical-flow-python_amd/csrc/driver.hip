@@ -15,9 +15,10 @@
 //   kernels_img.hip    colour, filters, resampling, pyramids, ROF
 //   kernels_flow.hip   warp, derivatives, system assembly, occlusion, medians, weighted median
 //   kernels_track.hip  point tracker: advance and seed steps
-//   kernels_fuse.hip   temporal denoising: flow composition, frame fusion
+//   kernels_fuse.hip   temporal denoising: flow composition, frame fusion, the fusion's weights
 //   kernels_noise.hip  noise-level estimation: the two estimators' keys, the exact radix selection of their median
 //   kernels_upsample.hip reduced-resolution flow: the box reduction of a frame, the edge-aware upsampling of a flow
+//   kernels_sr.hip     multi-frame super-resolution: the resampling along the flows, the back-projection step
 //   kernels_motion.hip global motion: the passes of the robust parametric fit, the affine warp
 //   kernels_layers.hip layered motion segmentation (uses the fit's passes)
 //   kernels_solve.hip  what the solvers share (partials, fixed-order sums, residual), norm and residual diagnostics
@@ -37,7 +38,8 @@
 //   host_session.hip what the frame-sequence sessions share: lookup and free, open and push prologues, delayed emission, the flow-scale switch
 //   host_track.hip  point tracker: advance and seed steps, stage entries, the session
 //   host_noise.hip  noise-level estimation: the pair and single-frame estimators, their stage entries
-//   host_fuse.hip   temporal denoising: flow composition, frame fusion, stage entries, the session and its automatic sigma
+//   host_fuse.hip   temporal denoising: flow composition, frame fusion, stage entries, the rings of frames and pairs, the session and its automatic sigma
+//   host_sr.hip     multi-frame super-resolution: the resampling and back-projection, the stage entry, the session
 //   host_motion.hip global motion: the robust parametric fit, the affine warp, path smoothing, the stabiliser session
 //   host_layers.hip layered motion segmentation: hypotheses, extraction, joint rounds, the stage entry
 //   batch.hip       lanes, of_pairs_run[_host], pair pool, slot copies, RCCL gather
@@ -66,6 +68,7 @@
 #include "kernels_fuse.hip"
 #include "kernels_noise.hip"
 #include "kernels_upsample.hip"
+#include "kernels_sr.hip"
 #include "kernels_motion.hip"
 #include "kernels_layers.hip"
 #include "kernels_solve.hip"
@@ -84,6 +87,7 @@
 #include "host_track.hip"
 #include "host_noise.hip"
 #include "host_fuse.hip"
+#include "host_sr.hip"
 #include "host_motion.hip"
 #include "host_layers.hip"
 #include "batch.hip"

@@ -167,7 +167,8 @@ struct PairPool {
 // frame size, the parameters, a ring of the last frames, the delayed-emission
 // state and the device allocations, which are the session's own and outlive
 // the arena's per-call reset.  A context holds at most one of each kind.
-enum { SES_TRACK, SES_DENOISE, SES_STAB, SES_KINDS };
+// of_session_set_flow_scale names the first SES_SCALE_KINDS of them.
+enum { SES_TRACK, SES_DENOISE, SES_STAB, SES_SR, SES_KINDS, SES_SCALE_KINDS = SES_SR };
 struct Session {
   int H = 0, W = 0, C = 0;
   of_params P;        // as given at open; every push starts from a copy
@@ -203,14 +204,18 @@ struct Tracker : Session {
   int *bcnt = nullptr;                       // the cell kernels' block counts, then the total
 };
 
-// the temporal denoiser (of_denoise_open, host_fuse.hip): a ring of 2R+1
-// frames and rings of the last 2R adjacent pairs' flows and forward-backward
-// states
-struct Denoiser : Session {
+// What the temporal denoiser and the super-resolver keep (host_fuse.hip): a
+// ring of 2R+1 frames and rings of the last 2R adjacent pairs' flows and
+// forward-backward states
+struct PairRing : Session {
   int pitch = 0;
-  of_fuse_opts opt;
   float2 *fw[4] = {}, *bw[4] = {};         // pair (j, j+1) at j % 2R: pitched flows j -> j+1 and j+1 -> j
   uint8_t *sf[4] = {}, *sb[4] = {};        // their forward-backward states, H x W dense
+};
+
+// the temporal denoiser (of_denoise_open, host_fuse.hip)
+struct Denoiser : PairRing {
+  of_fuse_opts opt;
   // of_denoise_open_auto: sigma per emitted frame from the pair estimates
   // (host_noise.hip), kept on the host in the pairs' ring order
   bool auto_sigma = false;
@@ -218,6 +223,11 @@ struct Denoiser : Session {
   of_noise_estimate est[4] = {};           // pair (j, j+1) at j % 2R
   double last_sigma = 0;                   // what the last emitted frame was fused with
   bool emitted = false;
+};
+
+// the super-resolver (of_sr_open, host_sr.hip)
+struct SuperResolver : PairRing {
+  of_sr_opts opt;
 };
 
 // the stabiliser (of_stab_open, host_motion.hip): a ring of R+1 frames; the
@@ -367,7 +377,7 @@ struct of_ctx {
   std::vector<Slot> slots;
   HostStage *hs = nullptr;      // of_pairs_run_host staging (lazily created)
   PairPool *pool = nullptr;     // of_pairs_open streaming batch (lanes of its own)
-  Session *session[SES_KINDS] = {};  // of_tracks_open, of_denoise_open, of_stab_open: one of each
+  Session *session[SES_KINDS] = {};  // of_tracks_open, of_denoise_open, of_stab_open, of_sr_open: one of each
   std::vector<of_ctx *> lanes;  // of_pairs_run pipelines: own stream, arena and solver state
   Token big_own;                // (parent) the big-phase token its lanes share
   Token *big = nullptr;         // (lane) token held through phases of >= big_px pixels

@@ -1,5 +1,5 @@
 // host_session.hip — what the frame-sequence sessions of a context (point
-// tracker, temporal denoiser, stabiliser: Session, host_core.h) share: the
+// tracker, temporal denoiser, stabiliser, super-resolver: Session, host_core.h) share: the
 // words of their messages, lookup and free, the open and push prologues, the
 // bookkeeping of the delayed emitters and the switch to reduced-resolution
 // pairs (of_session_set_flow_scale).
@@ -11,7 +11,8 @@ struct SessionKind {
 };
 const SessionKind SESSION_KIND[SES_KINDS] = {{"point tracker", "of_tracks_", "point tracking"},
                                              {"temporal denoiser", "of_denoise_", "temporal fusion"},
-                                             {"stabiliser", "of_stab_", "global motion"}};
+                                             {"stabiliser", "of_stab_", "global motion"},
+                                             {"super-resolver", "of_sr_", "super-resolution"}};
 
 std::string session_not_open(int kind) {
   const SessionKind &K = SESSION_KIND[kind];
@@ -136,9 +137,9 @@ int of_session_set_flow_scale(of_ctx *c, int kinds, const of_upsample_opts *o) {
   if (!c) return OF_EINVAL;
   try {
     check_upsample_opts(o, true);
-    REQUIRE(kinds > 0 && kinds < (1 << SES_KINDS), OF_EINVAL, "kinds must name one or more of OF_SESSION_*");
+    REQUIRE(kinds > 0 && kinds < (1 << SES_SCALE_KINDS), OF_EINVAL, "kinds must name one or more of OF_SESSION_*");
     // every named session is checked before any is changed
-    for (int kind = 0; kind < SES_KINDS; ++kind) {
+    for (int kind = 0; kind < SES_SCALE_KINDS; ++kind) {
       if (!(kinds >> kind & 1)) continue;
       const Session *s = c->session[kind];
       REQUIRE(s, OF_EINVAL, session_not_open(kind));
@@ -146,7 +147,7 @@ int of_session_set_flow_scale(of_ctx *c, int kinds, const of_upsample_opts *o) {
               std::string("the ") + SESSION_KIND[kind].name +
                   " has estimated a pair already (set the flow scale before the second push)");
     }
-    for (int kind = 0; kind < SES_KINDS; ++kind)
+    for (int kind = 0; kind < SES_SCALE_KINDS; ++kind)
       if (kinds >> kind & 1) c->session[kind]->up = o->scale == 1 ? of_upsample_opts{1, 0, 0.0} : *o;
     return OF_OK;
   }

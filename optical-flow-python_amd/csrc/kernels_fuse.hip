@@ -1,7 +1,8 @@
 // kernels_fuse.hip — motion-compensated temporal denoising: chaining two
 // flows (k_flow_compose) and fusing a frame with its neighbours warped along
 // flows from the frame to each of them (k_fuse), every neighbour weighted per
-// pixel by how well its warped patch matches the frame's.  Frames are dense
+// pixel by how well its warped patch matches the frame's (k_fuse_weights gives
+// those weights on their own).  Frames are dense
 // H x W x C interleaved fp32, flows pitched float2, states dense H x W bytes
 // in of_fb_consistency's encoding.  All arithmetic in fp64 from the fp32
 // inputs with no contraction, in the order include/optflow.h states
@@ -79,90 +80,137 @@ __device__ __forceinline__ bool fuse_sample(const float *__restrict__ I, const f
   return true;
 }
 
+// The thread's place in its 32 x 8 tile (gx = tiles across; the grid is 1-D in
+// the XCD-aware order) and the geometry of the tile's LDS region for a window
+// of half-size r.
+struct FuseTile {
+  int i0, j0, ly, lx, i, j, tid;
+  bool own;
+  int LW, n_top, n_ring;  // LDS row length; halo ring: rows above and below, then the sides
+  size_t o;
+};
+__device__ __forceinline__ FuseTile fuse_tile(int H, int W, int r, int gx) {
+  FuseTile t;
+  const int tile = of_xcd_tile(blockIdx.x, gridDim.x);
+  const int tyi = tile / gx, txi = tile - tyi * gx;
+  t.i0 = tyi * FUSE_TH;
+  t.j0 = txi * FUSE_TW;
+  t.tid = threadIdx.x;
+  t.ly = t.tid / FUSE_TW;
+  t.lx = t.tid - t.ly * FUSE_TW;
+  t.i = t.i0 + t.ly;
+  t.j = t.j0 + t.lx;
+  t.own = t.i < H && t.j < W;
+  t.LW = FUSE_TW + 2 * r;
+  t.n_top = 2 * r * t.LW;
+  t.n_ring = t.n_top + 2 * r * FUSE_TH;
+  t.o = (size_t)t.i * W + t.j;
+  return t;
+}
+
+// vis_k and w_k of one neighbour at the thread's pixel, the whole block
+// together: the block writes D and the visibility of its tile plus an r-wide
+// halo to LDS -- every thread its own pixel, keeping the warped sample wk,
+// then the threads share the halo ring -- and after a barrier each visible
+// pixel sums its window from LDS in row-major order, so the result does not
+// depend on the tile geometry.  Ends in a barrier: the next neighbour
+// overwrites the LDS planes.  w is written only where the pixel is visible.
+__device__ __forceinline__ bool fuse_weight(const float *__restrict__ I, const float *__restrict__ N,
+                                            const float2 *__restrict__ F, const uint8_t *__restrict__ S,
+                                            const FuseTile &t, int H, int W, int P, int C, int r, double two_s2,
+                                            double h2, double *s_D, uint8_t *s_v, double (&wk)[FUSE_MAX_C], double &w) {
+  OF_NOCONTRACT
+  double D = 0.0;
+  const bool vis = t.own && fuse_sample(I, N, F, S, t.i, t.j, H, W, P, C, wk, D);
+  const int LW = t.LW, lo = (t.ly + r) * LW + t.lx + r;
+  s_D[lo] = vis ? D : 0.0;
+  s_v[lo] = vis ? 1 : 0;
+  for (int h = t.tid; h < t.n_ring; h += FUSE_TW * FUSE_TH) {
+    int a, b;  // position in the LDS region
+    if (h < t.n_top) {
+      a = h / LW;
+      b = h - a * LW;
+      a = a < r ? a : a + FUSE_TH;
+    } else {
+      const int q = h - t.n_top;
+      a = q / (2 * r);
+      b = q - a * (2 * r);
+      a += r;
+      b = b < r ? b : b + FUSE_TW;
+    }
+    const int y = t.i0 - r + a, x = t.j0 - r + b;
+    double hw[FUSE_MAX_C], hD = 0.0;
+    const bool hv = y >= 0 && y < H && x >= 0 && x < W && fuse_sample(I, N, F, S, y, x, H, W, P, C, hw, hD);
+    s_D[a * LW + b] = hv ? hD : 0.0;
+    s_v[a * LW + b] = hv ? 1 : 0;
+  }
+  __syncthreads();
+  if (vis) {
+    double Ssum = 0.0;
+    int m = 0;
+    for (int a = 0; a <= 2 * r; ++a)
+      for (int b = 0; b <= 2 * r; ++b) {
+        const int p = (t.ly + a) * LW + t.lx + b;
+        if (s_v[p]) {
+          Ssum = Ssum + s_D[p];
+          ++m;
+        }
+      }
+    const double d = Ssum / (double)(m * C);
+    const double e0 = d - two_s2;
+    const double e = e0 > 0.0 ? e0 : 0.0;
+    const double z = e / h2;
+    const double x = z < 1.0 ? z : 1.0;
+    w = (1.0 - x) * (1.0 - x);
+  }
+  __syncthreads();
+  return vis;
+}
+
 // One thread per pixel of a 32 x 8 tile, the loop over the n neighbours inside
-// (the pixel's frame value, acc and wsum stay in registers).  Per neighbour the
-// block writes D and the visibility of its tile plus an r-wide halo to LDS --
-// every thread its own pixel, keeping the warped sample, then the threads
-// share the halo ring -- and after a barrier each visible pixel sums its
-// window from LDS in row-major order, so the result does not depend on the
-// tile geometry.  gx = tiles across; the grid is 1-D in the XCD-aware order.
+// (the pixel's frame value, acc and wsum stay in registers); fuse_weight gives
+// every neighbour's weight.
 __global__ void __launch_bounds__(FUSE_TW *FUSE_TH)
 k_fuse(const float *__restrict__ I, FuseArgs A, int n, int H, int W, int P, int C, int r, double two_s2, double h2,
        int gx, float *__restrict__ out, float *__restrict__ out_w) {
   OF_NOCONTRACT
   __shared__ double s_D[FUSE_LDS];
   __shared__ uint8_t s_v[FUSE_LDS];
-  const int tile = of_xcd_tile(blockIdx.x, gridDim.x);
-  const int tyi = tile / gx, txi = tile - tyi * gx;
-  const int i0 = tyi * FUSE_TH, j0 = txi * FUSE_TW;
-  const int tid = threadIdx.x;
-  const int ly = tid / FUSE_TW, lx = tid - ly * FUSE_TW;
-  const int i = i0 + ly, j = j0 + lx;
-  const bool own = i < H && j < W;
-  const int LW = FUSE_TW + 2 * r;                         // LDS row length
-  const int n_top = 2 * r * LW, n_ring = n_top + 2 * r * FUSE_TH;  // halo ring: rows above and below, then the sides
-  const size_t o = (size_t)i * W + j;
+  const FuseTile t = fuse_tile(H, W, r, gx);
   double ctr[FUSE_MAX_C], acc[FUSE_MAX_C], wsum = 1.0;
 #pragma unroll
   for (int c = 0; c < FUSE_MAX_C; ++c) {
-    ctr[c] = own && c < C ? (double)I[o * C + c] : 0.0;
+    ctr[c] = t.own && c < C ? (double)I[t.o * C + c] : 0.0;
     acc[c] = ctr[c];
   }
   for (int k = 0; k < n; ++k) {
-    const float *__restrict__ N = A.neigh[k];
-    const float2 *__restrict__ F = A.flow[k];
-    const uint8_t *__restrict__ S = A.state[k];
-    double wk[FUSE_MAX_C] = {0.0, 0.0, 0.0, 0.0}, D = 0.0;
-    const bool vis = own && fuse_sample(I, N, F, S, i, j, H, W, P, C, wk, D);
-    const int lo = (ly + r) * LW + lx + r;
-    s_D[lo] = vis ? D : 0.0;
-    s_v[lo] = vis ? 1 : 0;
-    for (int h = tid; h < n_ring; h += FUSE_TW * FUSE_TH) {
-      int a, b;  // position in the LDS region
-      if (h < n_top) {
-        a = h / LW;
-        b = h - a * LW;
-        a = a < r ? a : a + FUSE_TH;
-      } else {
-        const int q = h - n_top;
-        a = q / (2 * r);
-        b = q - a * (2 * r);
-        a += r;
-        b = b < r ? b : b + FUSE_TW;
-      }
-      const int y = i0 - r + a, x = j0 - r + b;
-      double hw[FUSE_MAX_C], hD = 0.0;
-      const bool hv = y >= 0 && y < H && x >= 0 && x < W && fuse_sample(I, N, F, S, y, x, H, W, P, C, hw, hD);
-      s_D[a * LW + b] = hv ? hD : 0.0;
-      s_v[a * LW + b] = hv ? 1 : 0;
-    }
-    __syncthreads();
-    if (vis) {
-      double Ssum = 0.0;
-      int m = 0;
-      for (int a = 0; a <= 2 * r; ++a)
-        for (int b = 0; b <= 2 * r; ++b) {
-          const int p = (ly + a) * LW + lx + b;
-          if (s_v[p]) {
-            Ssum = Ssum + s_D[p];
-            ++m;
-          }
-        }
-      const double d = Ssum / (double)(m * C);
-      const double t = d - two_s2;
-      const double e = t > 0.0 ? t : 0.0;
-      const double z = e / h2;
-      const double x = z < 1.0 ? z : 1.0;
-      const double w = (1.0 - x) * (1.0 - x);
+    double wk[FUSE_MAX_C] = {0.0, 0.0, 0.0, 0.0}, w = 0.0;
+    if (fuse_weight(I, A.neigh[k], A.flow[k], A.state[k], t, H, W, P, C, r, two_s2, h2, s_D, s_v, wk, w)) {
 #pragma unroll
       for (int c = 0; c < FUSE_MAX_C; ++c) acc[c] = acc[c] + w * wk[c];
       wsum = wsum + w;
     }
-    __syncthreads();  // the next neighbour overwrites the LDS planes
   }
-  if (!own) return;
+  if (!t.own) return;
 #pragma unroll
   for (int c = 0; c < FUSE_MAX_C; ++c)
-    if (c < C) out[o * C + c] = (float)(acc[c] / wsum);
-  if (out_w) out_w[o] = (float)wsum;
+    if (c < C) out[t.o * C + c] = (float)(acc[c] / wsum);
+  if (out_w) out_w[t.o] = (float)wsum;
+}
+
+// The neighbour weights on their own (of_fuse_weights): out_w[k] = (float)w_k,
+// 0 where the neighbour is not visible; n dense H x W planes.
+__global__ void __launch_bounds__(FUSE_TW *FUSE_TH)
+k_fuse_weights(const float *__restrict__ I, FuseArgs A, int n, int H, int W, int P, int C, int r, double two_s2,
+               double h2, int gx, float *__restrict__ out_w) {
+  OF_NOCONTRACT
+  __shared__ double s_D[FUSE_LDS];
+  __shared__ uint8_t s_v[FUSE_LDS];
+  const FuseTile t = fuse_tile(H, W, r, gx);
+  const size_t px = (size_t)H * W;
+  for (int k = 0; k < n; ++k) {
+    double wk[FUSE_MAX_C] = {0.0, 0.0, 0.0, 0.0}, w = 0.0;
+    const bool vis = fuse_weight(I, A.neigh[k], A.flow[k], A.state[k], t, H, W, P, C, r, two_s2, h2, s_D, s_v, wk, w);
+    if (t.own) out_w[(size_t)k * px + t.o] = vis ? (float)w : 0.0f;
+  }
 }

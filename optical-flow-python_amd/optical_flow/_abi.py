@@ -199,6 +199,18 @@ class OfUpsampleOpts(C.Structure):
     _fields_ = [("scale", C.c_int32), ("pad_", C.c_int32), ("range", C.c_double)]
 
 
+# multi-frame super-resolution (include/optflow.h, "Multi-frame super-resolution along the flow")
+SR_MIN_FACTOR, SR_MAX_FACTOR = 2, 4
+SR_MAX_NEIGHBOURS = 8
+SR_MIN_REACH, SR_MAX_REACH = 0.75, 1.5
+
+
+class OfSrOpts(C.Structure):
+    _fields_ = [("factor", C.c_int32), ("radius", C.c_int32), ("patch", C.c_int32), ("pad_", C.c_int32),
+                ("sigma", C.c_double), ("strength", C.c_double), ("reach", C.c_double), ("back", C.c_double),
+                ("alpha1", C.c_double), ("alpha2", C.c_double)]
+
+
 def penalty(kind, p0=1.0, p1=0.0):
     return OfPenalty(PENALTY[kind], 0, float(p0), float(p1))
 

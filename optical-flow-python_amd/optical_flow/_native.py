@@ -12,7 +12,7 @@ import numpy as np
 
 from optical_flow._abi import (OfParams, OfStats, OfCgGeometry, OfSolveRecord, OfProgressFn, OfTrackOpts, OfFuseOpts,
                                OfNoiseEstimate, OfMotionOpts, OfMotionFit, OfStabOpts, OfLayersOpts, OfMotionLayer,
-                               OfUpsampleOpts, OF_ABI_VERSION,
+                               OfUpsampleOpts, OfSrOpts, OF_ABI_VERSION,
                                OF_EINVAL, OF_ENOTSUP)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -101,6 +101,14 @@ _SIGS = {
                                        C.POINTER(OfUpsampleOpts), C.c_double, C.c_double, _fp, _fp, _u8p, _u8p,
                                        C.POINTER(OfStats), C.POINTER(OfStats)], C.c_int),
     "of_session_set_flow_scale": ([_vp, C.c_int, C.POINTER(OfUpsampleOpts)], C.c_int),
+    "of_fuse_weights": ([_vp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _u8p, C.POINTER(OfFuseOpts), _fp],
+                        C.c_int),
+    "of_super_resolve": ([_vp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _u8p, C.POINTER(OfSrOpts), _fp,
+                          _fp], C.c_int),
+    "of_sr_open": ([_vp, C.POINTER(OfParams), C.c_int, C.c_int, C.c_int, C.POINTER(OfSrOpts)], C.c_int),
+    "of_sr_push": ([_vp, _fp, _fp, _fp, _i32p], C.c_int),
+    "of_sr_flush": ([_vp, _fp, _fp, _i32p], C.c_int),
+    "of_sr_close": ([_vp], C.c_int),
     "of_segment_motion": ([_vp, _fp, C.c_int, C.c_int, _fp, _u8p, C.POINTER(OfLayersOpts), C.POINTER(OfMotionLayer),
                            _i32p, _u8p, _u8p], C.c_int),
     "of_compute_flow_base": ([_vp, C.POINTER(OfParams), _fp, C.c_int, C.c_int, C.c_int, _fp, C.c_int,

@@ -1,7 +1,7 @@
 """What the package's modules share around the C ABI: the argument validators
 (ValueError before the library or a context is touched), the method ->
 of_params step, and the base classes of the frame-sequence sessions
-(PointTracker, TemporalDenoiser, Stabilizer)."""
+(PointTracker, TemporalDenoiser, Stabilizer, SuperResolver)."""
 import ctypes as C
 
 import numpy as np
@@ -182,16 +182,19 @@ class DelayedSession(Session):
     @classmethod
     def run_clip(cls, frames, last, *args):
         """`frames` through a session cls(shape, *args): the frames it returns,
-        (T, H, W[, 3]) float64, and the session's attribute `last` after each,
+        (T,) + their shape, float64, and the session's attribute `last` after each,
         stacked, both by frame index; for a tuple of attribute names, a tuple
         of such stacks."""
         frames = _clip(frames)
-        out = np.empty((len(frames),) + frames[0].shape, dtype=np.float64)
+        out = None  # (T,) + the shape of the frames the session returns, which need not be the input's
         names = (last,) if isinstance(last, str) else tuple(last)
         extra = [[None] * len(frames) for _ in names]
         with cls(frames[0].shape, *args) as s:
             def take(r):
+                nonlocal out
                 if r is not None:
+                    if out is None:
+                        out = np.empty((len(frames),) + r[1].shape, dtype=np.float64)
                     out[r[0]] = r[1]
                     for e, name in zip(extra, names):
                         e[r[0]] = getattr(s, name)

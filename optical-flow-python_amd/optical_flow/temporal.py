@@ -56,7 +56,7 @@ def compose_flows(f, g, state_f=None, state_g=None, return_state=False):
     return (nat.interleaved(out), so) if return_state else nat.interleaved(out)
 
 
-def _frame_stack(center, neighbours):
+def _frame_stack(center, neighbours, least=1):
     center = np.asarray(center)
     if center.ndim not in (2, 3) or center.size == 0 or center.dtype.kind not in "fiu":
         raise ValueError(f"center must be a non-empty (H, W) or (H, W, C) array of numbers, got {center.dtype} "
@@ -65,12 +65,40 @@ def _frame_stack(center, neighbours):
     if not 1 <= Cc <= _abi.FUSE_MAX_CHANNELS:
         raise ValueError(f"frames must have 1..{_abi.FUSE_MAX_CHANNELS} channels, got {Cc}")
     neighbours = [np.asarray(x) for x in neighbours]
-    if not 1 <= len(neighbours) <= _abi.FUSE_MAX_NEIGHBOURS:
-        raise ValueError(f"1..{_abi.FUSE_MAX_NEIGHBOURS} neighbours, got {len(neighbours)}")
+    if not least <= len(neighbours) <= _abi.FUSE_MAX_NEIGHBOURS:
+        raise ValueError(f"{least}..{_abi.FUSE_MAX_NEIGHBOURS} neighbours, got {len(neighbours)}")
     for x in neighbours:
         if x.shape != center.shape or x.dtype.kind not in "fiu":
             raise ValueError(f"every neighbour must be a {center.shape} array of numbers, got {x.dtype} {x.shape}")
     return center, neighbours, Cc
+
+
+def _fuse_inputs(center, neighbours, flows, states, least=1):
+    """The arguments a fusion shares, validated and as the C entries take
+    them: (H, W, channels, n, center, neighbours, flows, states), the arrays
+    contiguous float32 / uint8, or None for what is absent."""
+    center, neighbours, Cc = _frame_stack(center, neighbours, least)
+    H, W = center.shape[:2]
+    _frame_size(H, W)
+    n = len(neighbours)
+    flows = list(flows)
+    if len(flows) != n:
+        raise ValueError(f"{n} neighbours but {len(flows)} flows")
+    flows = [_flow(f"flows[{k}]", f, (H, W)) for k, f in enumerate(flows)]
+    st = None
+    if states is not None:
+        states = list(states)
+        if len(states) != n:
+            raise ValueError(f"{n} neighbours but {len(states)} states")
+        if any(s is not None for s in states):
+            st = np.zeros((n, H, W), dtype=np.uint8)
+            for k, s in enumerate(states):
+                if s is not None:
+                    st[k] = _state(f"states[{k}]", s, H, W)
+    c32 = nat.f32(np.asarray(center, dtype=float))
+    n32 = nat.f32(np.stack([np.asarray(x, dtype=float) for x in neighbours])) if n else None
+    f32 = np.ascontiguousarray(np.stack([_planar32(f) for f in flows])) if n else None
+    return H, W, Cc, n, c32, n32, f32, st
 
 
 def fuse_frames(center, neighbours, flows, sigma=None, states=None, strength=4.0, patch=2, return_weight=False):
@@ -86,35 +114,28 @@ def fuse_frames(center, neighbours, flows, sigma=None, states=None, strength=4.0
     (2 patch + 1)^2 window to the warped neighbour is at most 2 sigma^2 (what
     noise of standard deviation `sigma` explains) and falls to exactly 0 at
     2 sigma^2 + (strength sigma)^2 (of_fuse_frames).  `sigma` is required."""
-    center, neighbours, Cc = _frame_stack(center, neighbours)
-    H, W = center.shape[:2]
-    _frame_size(H, W)
-    n = len(neighbours)
-    flows = list(flows)
-    if len(flows) != n:
-        raise ValueError(f"{n} neighbours but {len(flows)} flows")
-    flows = [_flow(f"flows[{k}]", f, (H, W)) for k, f in enumerate(flows)]
+    H, W, Cc, n, c32, n32, f32, st = _fuse_inputs(center, neighbours, flows, states)
     opts = _fuse_opts(sigma, 1, strength, patch)
-    st = None
-    if states is not None:
-        states = list(states)
-        if len(states) != n:
-            raise ValueError(f"{n} neighbours but {len(states)} states")
-        if any(s is not None for s in states):
-            st = np.zeros((n, H, W), dtype=np.uint8)
-            for k, s in enumerate(states):
-                if s is not None:
-                    st[k] = _state(f"states[{k}]", s, H, W)
-    c32 = nat.f32(np.asarray(center, dtype=float))
-    n32 = nat.f32(np.stack([np.asarray(x, dtype=float) for x in neighbours]))
-    f32 = np.ascontiguousarray(np.stack([_planar32(f) for f in flows]))
-    out = np.empty(center.shape, dtype=np.float32)
+    out = np.empty(c32.shape, dtype=np.float32)
     wgt = np.empty((H, W), dtype=np.float32) if return_weight else None
     ctx = nat.context()
     ctx.check(ctx.lib.of_fuse_frames(ctx.handle, nat.ptr(c32), H, W, Cc, n, nat.ptr(n32), nat.ptr(f32), nat.u8ptr(st),
                                      C.byref(opts), nat.ptr(out), nat.ptr(wgt)))
     out = out.astype(np.float64)
     return (out, wgt.astype(np.float64)) if return_weight else out
+
+
+def fuse_weights(center, neighbours, flows, sigma=None, states=None, strength=4.0, patch=2):
+    """The weight every neighbour gets in fuse_frames with the same arguments:
+    (n, H, W) float64 in 0..1, 0 where the neighbour does not count at the
+    pixel (of_fuse_weights)."""
+    H, W, Cc, n, c32, n32, f32, st = _fuse_inputs(center, neighbours, flows, states)
+    opts = _fuse_opts(sigma, 1, strength, patch)
+    wgt = np.empty((n, H, W), dtype=np.float32)
+    ctx = nat.context()
+    ctx.check(ctx.lib.of_fuse_weights(ctx.handle, nat.ptr(c32), H, W, Cc, n, nat.ptr(n32), nat.ptr(f32),
+                                      nat.u8ptr(st), C.byref(opts), nat.ptr(wgt)))
+    return wgt.astype(np.float64)
 
 
 class TemporalDenoiser(DelayedSession):
