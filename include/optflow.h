@@ -193,9 +193,10 @@ int of_set_option(of_ctx *ctx, int option, int value);
  *                         buffer): flat across repeated pairs of one size; plus
  *                         an open point tracker's (of_tracks_open) and an open
  *                         temporal denoiser's (of_denoise_open), an open
- *                         stabiliser's (of_stab_open) and an open
- *                         super-resolver's (of_sr_open) buffers, which leave the
- *                         count again at their close */
+ *                         stabiliser's (of_stab_open), an open
+ *                         super-resolver's (of_sr_open) and an open
+ *                         inpainter's (of_inpaint_open) buffers, which leave
+ *                         the count again at their close */
 #define OF_OPT_DEVICE_BYTES 4
 /*   OF_OPT_RCCL_NRANKS    ranks of the context's RCCL communicator as RCCL
  *                         reports them (ncclCommCount; 0 before of_rccl_init) */
@@ -1108,6 +1109,116 @@ int of_sr_open(of_ctx *ctx, const of_params *params, int H, int W, int C, const 
 int of_sr_push(of_ctx *ctx, const float *frame, float *out, float *out_support, int32_t *out_index);
 int of_sr_flush(of_ctx *ctx, float *out, float *out_support, int32_t *out_index);
 int of_sr_close(of_ctx *ctx);
+
+/*
+ * Flow-guided video inpainting.  The caller marks a region in every frame of a
+ * clip (an object to remove); the region is filled with what the other frames
+ * show there, carried along the motion (Huang et al. 2016; Xu et al. 2019,
+ * without their networks).  Under the marks the flows are completed from their
+ * surroundings by the solver itself (a data weight of 0, "Per-pixel data-term
+ * weights" above); a marked pixel then walks through the completed flows of
+ * the adjacent pairs until it lands on a pixel that some frame really saw.
+ * Everything in double from the fp32 or byte inputs, no fma contraction, in
+ * exactly the order written (a numpy float64 restatement gives the same bits);
+ * bil and inside as defined above ("Using a flow on an image"); frames
+ * H x W x C interleaved, flows planar 2 x H x W, masks H x W bytes, a nonzero
+ * byte marking a pixel to be replaced.  H * W >= 2^31: OF_ENOTSUP.  Any option
+ * out of range or not finite: OF_EINVAL, checked on the host before any launch
+ * (every entry checks the whole struct).
+ *
+ * Grown mask:  D = grow(M, g):  D(i,j) = 1 where any M(i+a, j+b) != 0 with
+ * |a|, |b| <= g inside the frame, else 0; g = 0 gives M != 0.
+ *
+ * Pair weight of frames j and j+1 with grown masks D_j, D_j+1:
+ *   w(i,j) = 0.0f where grow(D_j | D_j+1, margin) is set, else 1.0f
+ * so the data term of both flows of the pair is off under the holes of either
+ * frame, margin pixels around them, and where the other frame's hole may land.
+ * The frames themselves go into the estimate unchanged: the object's own
+ * pixels are plausible content for the smoothness term to start from.
+ *
+ * Fill of frame t from the frames I_s, the grown masks D_s and the flows fw_s
+ * (s -> s+1) and bw_s (s+1 -> s) of the adjacent pairs within `radius` of t.
+ * A pixel (i, j) with D_t(i,j) == 0: out = the frame's own value, status
+ * OF_INPAINT_KEPT, both hop counts 0.  A pixel with D_t(i,j) != 0 walks
+ * forward (flows fw_t, fw_t+1, ..., targets t+1, t+2, ...) and backward (flows
+ * bw_t-1, bw_t-2, ..., targets t-1, t-2, ...).  Each walk starts from r = i,
+ * q = j without a hit; for hop d = 1 .. radius, while the target frame exists:
+ *   u = bil(F.x, r, q); v = bil(F.y, r, q)        (F: the flow of this hop)
+ *   u or v not finite                        -> the walk ends without a hit
+ *   r = r + v; q = q + u
+ *   !inside(r, q)                            -> the walk ends without a hit
+ *   i0 = floor(r); j0 = floor(q); i1 = min(i0+1, H-1); j1 = min(j0+1, W-1)
+ *   any of D_target at (i0,j0) (i0,j1) (i1,j0) (i1,j1) nonzero -> next hop
+ *   otherwise: colour_c = bil(I_target_c, r, q); hops = d; hit; the walk ends
+ * With a forward hit at df (colour cf) and a backward hit at db (colour cb):
+ *   out_c = (float)(((double)db*cf_c + (double)df*cb_c) / (double)(df + db))
+ * (the nearer frame counts more); with one hit (float) of its colour; with
+ * none the frame's own value.  Status OF_INPAINT_FILLED or OF_INPAINT_UNFILLED;
+ * out_hops holds df, then db (0 = no hit).  Flows of +-1e30 are finite: their
+ * walk ends at !inside.  The walk consults no forward-backward state: until it
+ * hits it moves only through grown holes, where that test says nothing, and the
+ * hit itself uses no flow.
+ *
+ * Known limits: no spatial fallback (a pixel that no frame within `radius`
+ * reveals comes back OF_INPAINT_UNFILLED), no seam or exposure blending; a hole
+ * bordered by two motions gets the smoothness term's blend of them; the marks
+ * must cover shadows and reflections themselves, `grow` only pads them.
+ */
+#define OF_INPAINT_KEPT 0
+#define OF_INPAINT_FILLED 1
+#define OF_INPAINT_UNFILLED 2
+#define OF_INPAINT_MAX_RADIUS 16
+#define OF_INPAINT_MAX_GROW 8
+#define OF_INPAINT_MAX_MARGIN 16
+#define OF_MASK_GROW_MAX 24
+typedef struct of_inpaint_opts {
+  int32_t radius;   /* frames on each side a walk may reach, 1..16 (8) */
+  int32_t grow;     /* g of the grown masks, 0..8 (2) */
+  int32_t margin;   /* session only: the pair weight's margin, 0..16 (4) */
+  int32_t pad_;
+} of_inpaint_opts;
+/* grow(a | b, g), b may be NULL, g 0..24: out_mask H x W bytes (0 / 1) and / or
+ * out_weight H x W fp32 (0.0f where the grown mask is set, else 1.0f, the pair
+ * weight when a and b are two frames' grown masks); either may be NULL, not
+ * both */
+int of_mask_grow(of_ctx *ctx, const uint8_t *a, const uint8_t *b, int H, int W, int g, uint8_t *out_mask,
+                 float *out_weight);
+/*
+ *   frames     : T x H x W x C, C 1..4
+ *   masks      : T x H x W bytes as the caller drew them; grown by opts->grow inside
+ *   fw, bw     : (T-1) x 2 x H x W, pair s = frames (s, s+1); NULL allowed when T == 1
+ *   t          : the frame to fill, 0 .. T-1
+ *   out        : H x W x C
+ *   out_status : H x W bytes, or NULL
+ *   out_hops   : 2 x H x W bytes (df, db), or NULL
+ */
+int of_inpaint_fill(of_ctx *ctx, const float *frames, const uint8_t *masks, const float *fw, const float *bw, int T,
+                    int H, int W, int C, int t, const of_inpaint_opts *opts, float *out, uint8_t *out_status,
+                    uint8_t *out_hops);
+/*
+ * The inpainter session: one per context, beside the other kinds; a delayed
+ * emitter of radius opts->radius like the denoiser.  It keeps the last
+ * 2 radius + 1 frames and grown masks and both flows of the last 2 radius
+ * adjacent pairs on the device; its buffers count in OF_OPT_DEVICE_BYTES from
+ * open to close.  C is 1 or 3.  A push stores the frame and grow(mask, grow)
+ * and, from the second frame on, estimates the pair (previous, this): the pair
+ * weight w is built on the device and both directions are estimated from zero
+ * flows with a fresh copy of the open's params, bitwise
+ * of_estimate_flow_weighted(previous, this, w) and
+ * of_estimate_flow_weighted(this, previous, w).  Open therefore refuses what
+ * that entry refuses (a general spatial_filters list, AltBA: OF_ENOTSUP).
+ * Frame t is emitted, once frame t + radius is in or at the flush, as
+ * of_inpaint_fill of that frame with the frames and pairs within radius that
+ * exist; a clip of one frame comes back as it is, its marked pixels
+ * OF_INPAINT_UNFILLED.  out: H x W x C; out_status: H x W bytes or NULL;
+ * *out_index: the emitted frame or -1.  A push after a flush and a second open
+ * are refused (OF_EINVAL).  It is not a kind of_session_set_flow_scale takes.
+ */
+int of_inpaint_open(of_ctx *ctx, const of_params *params, int H, int W, int C, const of_inpaint_opts *opts);
+int of_inpaint_push(of_ctx *ctx, const float *frame, const uint8_t *mask, float *out, uint8_t *out_status,
+                    int32_t *out_index);
+int of_inpaint_flush(of_ctx *ctx, float *out, uint8_t *out_status, int32_t *out_index);
+int of_inpaint_close(of_ctx *ctx);
 
 /*
  * Layered motion segmentation.  of_fit_motion finds one motion, the dominant

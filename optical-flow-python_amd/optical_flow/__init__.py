@@ -11,6 +11,8 @@ from optical_flow.tracking import (advance_points, seed_points, PointTracker, tr
                                    TRACK_ALIVE, TRACK_OCCLUDED, TRACK_LEFT_FRAME, TRACK_MOTION_BOUNDARY)
 from optical_flow.temporal import compose_flows, fuse_frames, fuse_weights, TemporalDenoiser, denoise_frames
 from optical_flow.superres import super_resolve, SuperResolver, super_resolve_frames
+from optical_flow.inpaint import (grow_mask, pair_weight, propagate_fill, VideoInpainter, inpaint_frames,
+                                  INPAINT_KEPT, INPAINT_FILLED, INPAINT_UNFILLED)
 from optical_flow.noise import estimate_noise, NoiseEstimate
 from optical_flow.motion import (fit_motion, warp_affine, Stabilizer, stabilize_frames, MotionFit, segment_motion,
                                  MotionLayers, MotionLayer, LAYER_NONE)
@@ -31,4 +33,6 @@ __all__ = ['estimate_flow', 'estimate_flow_batch', 'PairStream', 'read_flo', 'wr
            'TRACK_LEFT_FRAME', 'TRACK_MOTION_BOUNDARY', 'compose_flows', 'fuse_frames', 'TemporalDenoiser',
            'denoise_frames', 'fit_motion', 'warp_affine', 'Stabilizer', 'stabilize_frames', 'MotionFit',
            'segment_motion', 'MotionLayers', 'MotionLayer', 'LAYER_NONE', 'estimate_noise', 'NoiseEstimate',
-           'reduce_frame', 'upsample_flow', 'fuse_weights', 'super_resolve', 'SuperResolver', 'super_resolve_frames']
+           'reduce_frame', 'upsample_flow', 'fuse_weights', 'super_resolve', 'SuperResolver', 'super_resolve_frames',
+           'grow_mask', 'pair_weight', 'propagate_fill', 'VideoInpainter', 'inpaint_frames', 'INPAINT_KEPT',
+           'INPAINT_FILLED', 'INPAINT_UNFILLED']

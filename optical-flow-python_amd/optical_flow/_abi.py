@@ -211,6 +211,17 @@ class OfSrOpts(C.Structure):
                 ("alpha1", C.c_double), ("alpha2", C.c_double)]
 
 
+# flow-guided video inpainting (include/optflow.h, "Flow-guided video inpainting"): status bytes and ranges
+OF_INPAINT_KEPT, OF_INPAINT_FILLED, OF_INPAINT_UNFILLED = 0, 1, 2
+INPAINT_MAX_RADIUS, INPAINT_MAX_GROW, INPAINT_MAX_MARGIN = 16, 8, 16
+INPAINT_MAX_CHANNELS = 4
+MASK_GROW_MAX = 24
+
+
+class OfInpaintOpts(C.Structure):
+    _fields_ = [("radius", C.c_int32), ("grow", C.c_int32), ("margin", C.c_int32), ("pad_", C.c_int32)]
+
+
 def penalty(kind, p0=1.0, p1=0.0):
     return OfPenalty(PENALTY[kind], 0, float(p0), float(p1))
 

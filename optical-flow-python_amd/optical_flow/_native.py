@@ -12,7 +12,7 @@ import numpy as np
 
 from optical_flow._abi import (OfParams, OfStats, OfCgGeometry, OfSolveRecord, OfProgressFn, OfTrackOpts, OfFuseOpts,
                                OfNoiseEstimate, OfMotionOpts, OfMotionFit, OfStabOpts, OfLayersOpts, OfMotionLayer,
-                               OfUpsampleOpts, OfSrOpts, OF_ABI_VERSION,
+                               OfUpsampleOpts, OfSrOpts, OfInpaintOpts, OF_ABI_VERSION,
                                OF_EINVAL, OF_ENOTSUP)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -151,6 +151,13 @@ _SIGS = {
     "of_solver_geometry": ([C.c_int, C.c_int, C.c_int, C.POINTER(OfCgGeometry)], C.c_int),
     "of_set_solve_log": ([_vp, C.c_int], C.c_int),
     "of_solve_log": ([_vp, C.c_int, C.POINTER(OfSolveRecord), _ip], C.c_int),
+    "of_mask_grow": ([_vp, _u8p, _u8p, C.c_int, C.c_int, C.c_int, _u8p, _fp], C.c_int),
+    "of_inpaint_fill": ([_vp, _fp, _u8p, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                         C.POINTER(OfInpaintOpts), _fp, _u8p, _u8p], C.c_int),
+    "of_inpaint_open": ([_vp, C.POINTER(OfParams), C.c_int, C.c_int, C.c_int, C.POINTER(OfInpaintOpts)], C.c_int),
+    "of_inpaint_push": ([_vp, _fp, _u8p, _fp, _u8p, _i32p], C.c_int),
+    "of_inpaint_flush": ([_vp, _fp, _u8p, _i32p], C.c_int),
+    "of_inpaint_close": ([_vp], C.c_int),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

@@ -1,7 +1,7 @@
 """What the package's modules share around the C ABI: the argument validators
 (ValueError before the library or a context is touched), the method ->
 of_params step, and the base classes of the frame-sequence sessions
-(PointTracker, TemporalDenoiser, Stabilizer, SuperResolver)."""
+(PointTracker, TemporalDenoiser, Stabilizer, SuperResolver, VideoInpainter)."""
 import ctypes as C
 
 import numpy as np
