@@ -16,7 +16,7 @@
 // block-Jacobi splitting A = D - N, B = D^-1 N:
 //   M^-1 = (c0 + c1 B + ... + c5 B^5) D^-1,
 // the Chebyshev polynomial that minimises max |1 - X p(X)| for the spectrum
-// of X = D^-1 A = I - B on [a, 2] (a = 0.04, 0.02 for the robust GNC stages;
+// of X = D^-1 A = I - B on [a, 2] (a = 0.04, 0.01 for the robust GNC stages;
 // host: cheb_poly; 2 bounds the spectrum because D + N is positive
 // semidefinite).  p > 0 there, so M is SPD.  (Round 1 used degree 3: 0.54x
 // the iterations of a first-order Neumann preconditioner, 0.27x of block
@@ -125,7 +125,8 @@ __device__ __forceinline__ cg_f4 cgr_diag_raw(const CgRaw &c, cg_f4 f) {
 // per SIMD and 1.6x the rows read.)  Here 74 KB of LDS per block allow 2 blocks per CU (R = 39 at
 // 1080p) and a step costs only the heaviest wave's share.  Stage lags follow
 // from one barrier per step: a stage reads rows of another wave produced at
-// earlier steps; the band is walked for n in [r0 - 8, r1 + 11] so that every
+// earlier steps; the band is walked for n in [r0 - 8, r1 + 11] (an odd band,
+// walked bottom to top, to r1 + 12: stage F's T5 seam edge) so that every
 // row a required stage reads was produced.
 // Rejected variants of this kernel (record split over waves 0 / 3, register
 // record rings, raw-D stage E, pair-block splitting, trimmed drain loads)
@@ -331,7 +332,9 @@ __global__ __launch_bounds__(256) void k_cgs(PcgArgs g, int k, int R, int nbands
     return (dm0 ? p.x + p.y : 0.f) + (dm1 ? q.x + q.y : 0.f);
   };
   const cg_f4 zero4 = {0.f, 0.f, 0.f, 0.f};
-  const int ns = r0 - 8, ne = r1 + 11;
+  // (a flipped band walks one step further: stage F's T5 there also takes the
+  // edge below its last virtual row, which needs v2 of row r1)
+  const int ns = r0 - 8, ne = r1 + 11 + (flip ? 1 : 0);
 
   // zeroed rings: rows above the band that no required stage reads
   {
@@ -570,11 +573,21 @@ __global__ __launch_bounds__(256) void k_cgs(PcgArgs g, int k, int R, int nbands
           const cg_f4 vu = V2[R2(-13)];
           V2[R2(-12)] = v2;
           const int o = n - 12;
+          // T5's vertical edge (o - 1, o), once over the level: the walk of
+          // an odd band is flipped, so both of its seam edges lie above one of
+          // its virtual rows r0 .. r1 (the band below it in the walk is even
+          // and cannot take the edge: it has no v2 past its own last row);
+          // an even band then takes its inner edges only
+          const bool vedge = flip ? o >= r0 && o <= r1 : o > r0 && o < r1;
           if (inband(o)) {
             const cg_f2 w0 = cg_lo(v2), w1 = cg_hi(v2);
-            const cg_f2 h0 = cg_left2(q7.wx[1]) * cg_left2(w1) + wy7[0] * cg_lo(vu);
-            const cg_f2 h1 = q7.wx[0] * w0 + wy7[1] * cg_hi(vu);
+            const cg_f2 h0 = cg_left2(q7.wx[1]) * cg_left2(w1);
+            const cg_f2 h1 = q7.wx[0] * w0;
             const cg_f4 t = (c3 * v1 + c4 * v2) * nv + (2.0f * c5) * v2 * cg_cat(h0, h1);
+            acc[2] += (double)((dm0 ? t.x + t.y : 0.f) + (dm1 ? t.z + t.w : 0.f));
+          }
+          if (vedge) {
+            const cg_f4 t = (2.0f * c5) * v2 * cg_cat(wy7[0] * cg_lo(vu), wy7[1] * cg_hi(vu));
             acc[2] += (double)((dm0 ? t.x + t.y : 0.f) + (dm1 ? t.z + t.w : 0.f));
           }
         }

@@ -448,8 +448,12 @@ def sparse_to_planes(A, H, W):
     coef[5] = np.asarray(A[k.ravel(), N + k.ravel()]).reshape(H, W)
     for comp in range(2):
         o = comp * N
-        coef[2 * comp][:, :-1] = -np.asarray(A[o + k[:, :-1].ravel(), o + k[:, 1:].ravel()]).reshape(H, W - 1)
-        coef[2 * comp + 1][:-1, :] = -np.asarray(A[o + k[:-1, :].ravel(), o + k[1:, :].ravel()]).reshape(H - 1, W)
+        # (one column / one row has no such edges, and scipy answers an empty
+        # index pair with one element, not none)
+        if W > 1:
+            coef[2 * comp][:, :-1] = -np.asarray(A[o + k[:, :-1].ravel(), o + k[:, 1:].ravel()]).reshape(H, W - 1)
+        if H > 1:
+            coef[2 * comp + 1][:-1, :] = -np.asarray(A[o + k[:-1, :].ravel(), o + k[1:, :].ravel()]).reshape(H - 1, W)
     R = planes_to_sparse(coef)
     if abs(R - A).max() > 1e-9 * max(1.0, abs(A).max()):
         raise NotImplementedError("A is not a symmetric 5-point + 2x2-coupling flow operator")
