@@ -13,7 +13,12 @@
 //
 // Kernel files, one family each, in dependency order like the host parts:
 //   kernels_img.hip    colour, filters, resampling, pyramids, ROF
-//   kernels_flow.hip   warp, derivatives, system assembly, occlusion, medians, weighted median
+//   kernels_sample.hip the fp64 clamped bilinear sample of frames and flows that the files from kernels_interp.hip on share
+//   kernels_warp.hip   warp of frame 2 and the data term's derivatives
+//   kernels_assemble.hip system assembly, from derivative planes or fused with the warp; the fp64 assembly
+//   kernels_flow.hip   flow update and occlusion, duv bookkeeping, forward-backward check, medians
+//   kernels_interp.hip image warp, frame interpolation: splat, resolve, fill, render
+//   kernels_wmf.hip    the weighted median
 //   kernels_track.hip  point tracker: advance and seed steps
 //   kernels_fuse.hip   temporal denoising: flow composition, frame fusion, the fusion's weights
 //   kernels_noise.hip  noise-level estimation: the two estimators' keys, the exact radix selection of their median
@@ -65,7 +70,12 @@
 #include <vector>
 
 #include "kernels_img.hip"
+#include "kernels_sample.hip"
+#include "kernels_warp.hip"
+#include "kernels_assemble.hip"
 #include "kernels_flow.hip"
+#include "kernels_interp.hip"
+#include "kernels_wmf.hip"
 #include "kernels_track.hip"
 #include "kernels_fuse.hip"
 #include "kernels_noise.hip"

@@ -1,5 +1,5 @@
 // host_flow.hip — the flow estimation itself: the assembly dispatch
-// (kernels_flow.hip), the lanes' token, progress reports, the per-level IRLS
+// (kernels_assemble.hip), the lanes' token, progress reports, the per-level IRLS
 // loops of the four methods, the coarse-to-fine GNC schedule and the
 // device-side estimate_flow in one and both directions.
 namespace {
@@ -38,7 +38,7 @@ OpArgs op_args(const of_params *P, double alpha, double lambda2) {
   return o;
 }
 
-// the assembly kernels' penalty mode (kernels_flow.hip, PenMode): the
+// the assembly kernels' penalty mode (kernels_assemble.hip, PenMode): the
 // quadratic stage or a robust stage whose penalties share one kind get a
 // specialised kernel, anything else the run-time form
 int pen_mode(const OpArgs &o) {
@@ -76,7 +76,7 @@ void check_weight(const Img &wgt, const OpArgs &o, const Img &coef) {
           "data weight: not a plane of this level");
 }
 
-// wgt: the level's data-weight plane, or p == nullptr (the unweighted kernels)
+// wgt: the level's data-weight plane, or p == nullptr (the <false, ...> kernels)
 void flow_operator(of_ctx *c, const OpArgs &o, const F2 &uv, const F2 *duv, const Img &It, const Img &Ix,
                    const Img &Iy, const F2 *uvhat, const Img &coef, const F2 &rhs, const Img &wgt = Img()) {
   Grid2 g = grid2(uv.H, uv.W);
@@ -86,18 +86,13 @@ void flow_operator(of_ctx *c, const OpArgs &o, const F2 &uv, const F2 *duv, cons
            It.C, (const float2 *)(uvhat ? uvhat->p : nullptr), uv.H, uv.W, uv.P, coef.ps(), coef.p, rhs.p, w...);
   };
   const int m = uvhat ? OF_PM_ANY : pen_mode(o);
-  if (wgt.p) {
-    check_weight(wgt, o, coef);
-    auto f = [&](auto kern) { go(kern, (const float *)wgt.p); };
-    OF_BY_PM(m, k_flow_operator_w, )
-    return;
-  }
-  auto f = [&](auto kern) { go(kern); };
+  if (wgt.p) check_weight(wgt, o, coef);
   if (o.f64) {
-    f(k_flow_operator_f64);
+    go(k_flow_operator_f64);
     return;
   }
-  OF_BY_PM(m, k_flow_operator, )
+  auto f = [&](auto kern) { go(kern, (const float *)wgt.p); };
+  if (wgt.p) { OF_BY_PM(m, k_flow_operator, true, ) } else { OF_BY_PM(m, k_flow_operator, false, ) }
 }
 
 // partial_deriv + flow_operator fused (k_warp_operator): no It / Ix / Iy
@@ -105,15 +100,15 @@ void flow_operator(of_ctx *c, const OpArgs &o, const F2 &uv, const F2 *duv, cons
 bool can_fuse_warp_op(const of_ctx *c, const OpArgs &o, int nc) {
   return c->opt_fused_warp && !o.f64 && (nc == 1 || nc == 3);
 }
-// calls f(kernel) with the instantiation of KT for the interpolation, the
-// channel count (1 or 3) and the penalty mode
-#define OF_BY_INTERP_NC_PM(interp, one, m, KT)                                                \
+// calls f(kernel) with the instantiation of KT for the weight flag WT, the
+// interpolation, the channel count (1 or 3) and the penalty mode
+#define OF_BY_INTERP_NC_PM(WT, interp, one, m, KT)                                            \
   if (interp == OF_INTERP_BICUBIC) {                                                          \
-    if (one) { OF_BY_PM(m, KT, 1, 1, ) } else { OF_BY_PM(m, KT, 1, 3, ) }                      \
+    if (one) { OF_BY_PM(m, KT, WT, 1, 1, ) } else { OF_BY_PM(m, KT, WT, 1, 3, ) }              \
   } else if (interp == OF_INTERP_CUBIC) {                                                     \
-    if (one) { OF_BY_PM(m, KT, 0, 1, ) } else { OF_BY_PM(m, KT, 0, 3, ) }                      \
+    if (one) { OF_BY_PM(m, KT, WT, 0, 1, ) } else { OF_BY_PM(m, KT, WT, 0, 3, ) }              \
   } else {                                                                                    \
-    if (one) { OF_BY_PM(m, KT, 2, 1, ) } else { OF_BY_PM(m, KT, 2, 3, ) }                      \
+    if (one) { OF_BY_PM(m, KT, WT, 2, 1, ) } else { OF_BY_PM(m, KT, WT, 2, 3, ) }              \
   }
 void warp_operator(of_ctx *c, const LevelDeriv &L, int interp, const OpArgs &o, const F2 &uv, const Img &coef,
                    const F2 &rhs, const Img &wgt = Img()) {
@@ -124,18 +119,17 @@ void warp_operator(of_ctx *c, const LevelDeriv &L, int interp, const OpArgs &o, 
   const char *name = interp == OF_INTERP_BICUBIC ? "warp_operator_hermite"
                      : interp == OF_INTERP_CUBIC ? "warp_operator_bspline"
                                                  : "warp_operator_bilinear";
-  auto go = [&](auto kern, auto... w) {
-    launch(c, name, kern, g.grid, g.block, 0, L.args, o, u, uv.H, uv.W, uv.P, ps, coef.p, rhs.p, w...);
+  auto f = [&](auto kern) {
+    launch(c, name, kern, g.grid, g.block, 0, L.args, o, u, uv.H, uv.W, uv.P, ps, coef.p, rhs.p,
+           (const float *)wgt.p);
   };
   const int m = pen_mode(o);
   const bool one = L.args.nc == 1;
   if (wgt.p) {
     check_weight(wgt, o, coef);
-    auto f = [&](auto kern) { go(kern, (const float *)wgt.p); };
-    OF_BY_INTERP_NC_PM(interp, one, m, k_warp_operator_w)
+    OF_BY_INTERP_NC_PM(true, interp, one, m, k_warp_operator)
   } else {
-    auto f = [&](auto kern) { go(kern); };
-    OF_BY_INTERP_NC_PM(interp, one, m, k_warp_operator)
+    OF_BY_INTERP_NC_PM(false, interp, one, m, k_warp_operator)
   }
 }
 

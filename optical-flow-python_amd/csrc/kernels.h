@@ -3,6 +3,7 @@
 #include "common.h"
 
 #define OF_BSPL_K 16
+#define OF_MAX_NC 4  // image channels per frame the host accepts
 
 struct Taps {  // small correlation kernel (<= 5x5)
   float w[25];

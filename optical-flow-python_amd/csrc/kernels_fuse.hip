@@ -7,7 +7,8 @@
 // in of_fb_consistency's encoding.  All arithmetic in fp64 from the fp32
 // inputs with no contraction, in the order include/optflow.h states
 // (of_flow_compose, of_fuse_frames), so a numpy float64 restatement gives the
-// same bits.  H * W < 2^31 (checked on the host).
+// same bits.  H * W < 2^31 (checked on the host).  Expects kernels_sample.hip
+// (in_frame, bil_tap, bil_at, bil2) and kernels_track.hip (trk_near) before it.
 #include "kernels.h"
 
 // out = f followed by g: the pixel's f, plus g sampled where f lands.  sf / sg
@@ -29,7 +30,7 @@ k_flow_compose(const float2 *__restrict__ f, const float2 *__restrict__ g, int H
       continue;
     }
     double gu, gv;
-    trk_bil2(g, W, P, bil_tap(r, q, H, W), gu, gv);
+    bil2(g, W, P, bil_tap(r, q, H, W), gu, gv);
     out[(size_t)i * P + j] = make_float2((float)(u + gu), (float)(v + gv));
     if (so) {
       const uint8_t s0 = sf ? sf[o] : (uint8_t)0;

@@ -7,6 +7,7 @@
 // All arithmetic in fp64 from the fp32 inputs with no contraction, in the
 // order include/optflow.h states (of_inpaint_fill), so a numpy float64
 // restatement gives the same bits.  H * W < 2^31 (checked on the host).
+// Expects kernels_sample.hip before it (in_frame, bil_tap, bil_at, bil2).
 #include "kernels.h"
 
 #define INP_MAX_R 16   // hops per direction
@@ -102,7 +103,7 @@ k_inpaint_fill(const float *__restrict__ I, const uint8_t *__restrict__ D, Inpai
         if (__builtin_amdgcn_ballot_w64(live) == 0) break;
         if (live) {
           double u, v;
-          trk_bil2(A.flow[dir][d], W, P, bil_tap(r, q, H, W), u, v);
+          bil2(A.flow[dir][d], W, P, bil_tap(r, q, H, W), u, v);
           live = __builtin_isfinite(u) && __builtin_isfinite(v);
           if (live) {
             r = r + v;

@@ -15,7 +15,8 @@
 // The arithmetic of a fit pass is stated once, here: the reset of a state
 // (mot_reset), the tile mapping (MOT_TILE), the usable-sample test
 // (mot_usable) and the closed-form solve (mot_solve) are what
-// kernels_layers.hip, included after this file, uses as well.
+// kernels_layers.hip, included after this file, uses as well.  Expects
+// kernels_sample.hip before it (in_frame, bil_tap, bil_at: k_warp_affine).
 #include "kernels.h"
 
 #define MOT_NS 13     // sums per pass: Sw Sx Sy Sxx Sxy Syy Su Sxu Syu Sv Sxv Syv Sr

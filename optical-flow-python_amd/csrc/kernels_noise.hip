@@ -6,7 +6,8 @@
 // of_fb_consistency's encoding.  All arithmetic in fp64 from the fp32 inputs
 // with no contraction, in the order include/optflow.h states
 // (of_estimate_noise_pair, of_estimate_noise), so a numpy float64 restatement
-// gives the same bits.  H * W < 2^31 (checked on the host).
+// gives the same bits.  H * W < 2^31 (checked on the host).  Expects
+// kernels_sample.hip before it (in_frame, bil_tap, bil_at).
 //
 // Keys are non-negative floats (+Inf included), so their bit patterns order
 // as unsigned integers; a slot without a usable sample holds NOISE_NOKEY, all

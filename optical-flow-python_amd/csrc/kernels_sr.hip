@@ -7,7 +7,8 @@
 // and limits on n and C hold here too).  All arithmetic in fp64 from the
 // fp32 inputs with no contraction, in the order include/optflow.h states
 // (of_super_resolve), so a numpy float64 restatement gives the same bits.
-// s*s*H*W < 2^31 (checked on the host).
+// s*s*H*W < 2^31 (checked on the host).  Expects kernels_sample.hip before
+// it (in_frame).
 #include "kernels.h"
 
 #define SR_MIN_S 2   // factors

@@ -7,25 +7,12 @@
 // arithmetic in fp64 from the fp32 inputs with no contraction, in the order
 // include/optflow.h states (of_track_advance, of_track_seed), so a numpy
 // float64 restatement gives the same bits.  H * W < 2^31 (checked on the host).
+// Expects kernels_sample.hip before it (in_frame, bil_tap, bil2); trk_near is
+// what kernels_fuse.hip, included after this file, uses as well.
 #include "kernels.h"
 
 #define TRK_BLOCK 256  // every kernel here: 1-D blocks of four waves
 
-// offset o of a dense H x W plane (bil_tap's) in the plane pitched to P
-__device__ __forceinline__ size_t trk_pitched(size_t o, int W, int P) {
-  return o + (size_t)((unsigned)o / (unsigned)W) * (size_t)(P - W);
-}
-// both components of a pitched flow at the taps
-__device__ __forceinline__ void trk_bil2(const float2 *__restrict__ A, int W, int P, const BilTap &b, double &u,
-                                         double &v) {
-  OF_NOCONTRACT
-  const float2 a00 = A[trk_pitched(b.o00, W, P)], a01 = A[trk_pitched(b.o01, W, P)];
-  const float2 a10 = A[trk_pitched(b.o10, W, P)], a11 = A[trk_pitched(b.o11, W, P)];
-  u = (1.0 - b.fr) * ((1.0 - b.fc) * (double)a00.x + b.fc * (double)a01.x) +
-      b.fr * ((1.0 - b.fc) * (double)a10.x + b.fc * (double)a11.x);
-  v = (1.0 - b.fr) * ((1.0 - b.fc) * (double)a00.y + b.fc * (double)a01.y) +
-      b.fr * ((1.0 - b.fc) * (double)a10.y + b.fc * (double)a11.y);
-}
 // near(x, n): the nearest index, clamped (NaN gives 0, so it never leaves the plane)
 __device__ __forceinline__ int trk_near(double x, int n) {
   return (int)fmin(fmax(floor(x + 0.5), 0.0), (double)(n - 1));
@@ -53,13 +40,13 @@ k_track_advance(const float2 *__restrict__ F, const float2 *__restrict__ B, int 
     return;
   }
   double u, v, bu, bv;
-  trk_bil2(F, W, P, bil_tap(yd, xd, H, W), u, v);
+  bil2(F, W, P, bil_tap(yd, xd, H, W), u, v);
   const double x1 = xd + u, y1 = yd + v;
   if (!in_frame(y1, x1, H, W)) {
     st_out[t] = OF_TRACK_LEFT_FRAME;
     return;
   }
-  trk_bil2(B, W, P, bil_tap(y1, x1, H, W), bu, bv);
+  bil2(B, W, P, bil_tap(y1, x1, H, W), bu, bv);
   const double du = u + bu, dv = v + bv;
   const double err = du * du + dv * dv;
   const double mag = u * u + v * v;

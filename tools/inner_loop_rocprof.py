@@ -17,8 +17,10 @@ path = sys.argv[1]
 H, W = (int(sys.argv[2]), int(sys.argv[3])) if len(sys.argv) > 3 else (1080, 1920)
 N = H * W
 rows = list(csv.DictReader(open(path)))
-fam = {"warp": "k_partial_deriv<1>", "assembly": "k_flow_operator", "warp_operator": "k_warp_operator<1",
-       "update": "k_update_occ", "cg": "k_cgs"}
+# the unweighted Hermite instances of the fused kernel: <false, 1, ...>, or
+# <1, ...> in a trace from before the weight flag led the template arguments
+fam = {"warp": "k_partial_deriv<1>", "assembly": "k_flow_operator",
+       "warp_operator": ("k_warp_operator<false, 1,", "k_warp_operator<1,"), "update": "k_update_occ", "cg": "k_cgs"}
 grid = {}
 for r in rows:
     name = r["Kernel_Name"].replace("void ", "")

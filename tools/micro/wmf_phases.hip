@@ -1,5 +1,5 @@
 // Per-phase timing of the weighted-median kernel at 1080p (Lab guide, h = 7):
-// kernels_flow.hip built with WMF_PHASE_TIMING records clock64() at the phase
+// kernels_wmf.hip built with WMF_PHASE_TIMING records clock64() at the phase
 // boundaries of every wave; prints the mean cycles per phase and the launch time.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -7,7 +7,7 @@
 #include <math.h>
 #include <vector>
 __device__ unsigned long long g_wmf_t[32400 * 8 + 64];
-#include "kernels_flow.hip"
+#include "kernels_wmf.hip"
 int main() {
   const int H = 1080, W = 1920, P = of_pitch(W), hsz = 7;
   const size_t ps = (size_t)H * P;

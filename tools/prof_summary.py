@@ -23,11 +23,18 @@ def short(name):
     (first launch, odd width; guide channels) are one kernel here"""
     n = name.split("(")[0].replace("void ", "")
     # the assembly kernels' penalty-mode instances are one kernel; the fused
-    # warp + assembly keeps its interpolation (different bytes per pixel)
-    if n.startswith("k_flow_operator<"):
-        return "k_flow_operator"
-    if n.startswith("k_warp_operator<"):
-        return "k_warp_operator<" + n[len("k_warp_operator<"):].split(",")[0].strip() + ">"
+    # warp + assembly keeps its interpolation (different bytes per pixel).
+    # Their first template argument is the weight flag: `false` is dropped,
+    # a weighted instance stays apart under its full name (as k_*_w did;
+    # traces from before the flag have neither and read as unweighted)
+    for op in ("k_flow_operator<", "k_warp_operator<"):
+        if n.startswith(op):
+            args = [a.strip() for a in n[len(op):].rstrip(">").split(",")]
+            if args[0] == "true":
+                return n
+            if args[0] == "false":
+                args = args[1:]
+            return op[:-1] if op == "k_flow_operator<" else op + args[0] + ">"
     for fam in ("k_cgs", "k_cgp", "k_cgn", "k_cg_small", "k_cg<", "k_wmf"):
         if n.startswith(fam):
             return fam.rstrip("<")

@@ -1,5 +1,5 @@
-"""GPU time of the weighted fused warp + assembly kernel (k_warp_operator_w)
-beside the unweighted one (k_warp_operator), per launch, from of_kernel_times.
+"""GPU time of the weighted fused warp + assembly kernel (k_warp_operator<true, ...>)
+beside the unweighted one (k_warp_operator<false, ...>), per launch, from of_kernel_times.
 
     python tools/weight_time.py [--size 1080 1920] [--method classic+nl-fast]
 
