@@ -194,8 +194,9 @@ int of_set_option(of_ctx *ctx, int option, int value);
  *                         an open point tracker's (of_tracks_open) and an open
  *                         temporal denoiser's (of_denoise_open), an open
  *                         stabiliser's (of_stab_open), an open
- *                         super-resolver's (of_sr_open) and an open
- *                         inpainter's (of_inpaint_open) buffers, which leave
+ *                         super-resolver's (of_sr_open), an open
+ *                         inpainter's (of_inpaint_open) and an open mask
+ *                         propagator's (of_masks_open) buffers, which leave
  *                         the count again at their close */
 #define OF_OPT_DEVICE_BYTES 4
 /*   OF_OPT_RCCL_NRANKS    ranks of the context's RCCL communicator as RCCL
@@ -1111,8 +1112,9 @@ int of_sr_flush(of_ctx *ctx, float *out, float *out_support, int32_t *out_index)
 int of_sr_close(of_ctx *ctx);
 
 /*
- * Flow-guided video inpainting.  The caller marks a region in every frame of a
- * clip (an object to remove); the region is filled with what the other frames
+ * Flow-guided video inpainting.  A region is marked in every frame of a clip
+ * (an object to remove; of_masks_* below carries one drawn mask through the
+ * clip); the region is filled with what the other frames
  * show there, carried along the motion (Huang et al. 2016; Xu et al. 2019,
  * without their networks).  Under the marks the flows are completed from their
  * surroundings by the solver itself (a data weight of 0, "Per-pixel data-term
@@ -1219,6 +1221,99 @@ int of_inpaint_push(of_ctx *ctx, const float *frame, const uint8_t *mask, float 
                     int32_t *out_index);
 int of_inpaint_flush(of_ctx *ctx, float *out, uint8_t *out_status, int32_t *out_index);
 int of_inpaint_close(of_ctx *ctx);
+
+/*
+ * Mask propagation: a marked object followed through a clip.  The binary mask
+ * of the previous frame is carried to the current one along the backward flow
+ * (current -> previous); a pixel whose flow cannot be trusted is decided by a
+ * colour-guided vote of its decided neighbours; a pixel with no decided
+ * neighbour stays unmarked and is reported as such; a small mode filter cleans
+ * the result.  of_masks_* followed by of_inpaint_* removes an object from one
+ * drawn mask.  Everything in double from the fp32 or byte inputs, no fma
+ * contraction, in exactly the order written (a numpy float64 restatement gives
+ * the same bits); bil and inside as defined above ("Using a flow on an image").
+ *   M : the previous mask, H x W bytes, nonzero = marked
+ *   G : the current frame, H x W x C interleaved fp32, C 1..4, the guide
+ *   B : the flow current -> previous, planar 2 x H x W
+ *   S : the forward-backward state of B, H x W bytes in of_fb_consistency's
+ *       encoding, or NULL (all 0)
+ * H * W >= 2^31: OF_ENOTSUP.  Any option out of range or not finite: OF_EINVAL,
+ * checked on the host before any launch (every entry checks the whole struct).
+ *
+ * Carry.  m = (M != 0) as 0.0 / 1.0; (u, v) = B(i,j).  Pixel (i, j) is decided
+ * when u and v are finite, inside(i + v, j + u) holds and S(i,j) == 0:
+ *   A(i,j) = (float)bil(m, i + v, j + u); label = A >= 0.5f; status OF_MASK_CARRIED
+ * Otherwise it is undecided and A(i,j) = -1.0f.
+ *
+ * Vote.  For each undecided pixel p = (i, j), with R = vote_radius: di = -R..R
+ * in the outer loop, dj = -R..R in the inner one, starting from num = den = 0.0
+ * and cnt = ones = 0; for every n = (i + di, j + dj) inside the frame that is
+ * decided:
+ *   D = 0.0; D = D + (G_c(p) - G_c(n))*(G_c(p) - G_c(n)) for c ascending; D = D / C
+ *   z = D / (range*range)
+ *   w = z < 1 ? (1 - z)*(1 - z) : 0                  (a non-finite G: z < 1 is false)
+ *   num = num + w*(double)A(n); den = den + w; cnt += 1; ones += A(n) >= 0.5f
+ * Then
+ *   den > 0         : label = num >= 0.5*den,  status OF_MASK_VOTED
+ *   else cnt > 0    : label = 2*ones >= cnt,   status OF_MASK_VOTED
+ *   else            : label = 0,               status OF_MASK_UNKNOWN
+ *
+ * Smooth.  One pass with radius s = smooth over the labels (s = 0: none): over
+ * the (2s+1)^2 window clipped to the frame, k = the labels equal to 1 and n =
+ * the window's pixels, all integer:
+ *   2k > n: 1;  2k < n: 0;  otherwise the pixel's own label
+ * The status plane is not touched.
+ *
+ * Known limits.  The vote needs colour contrast between object and
+ * surroundings: on the synthetic scene of the tests the mean IoU over 8 frames
+ * is 0.84 without and 0.98 with it (tests/test_mask_cpu.py); and it can only
+ * spread labels that some decided pixel carries, so an object whose whole area
+ * is undecided in one pair is lost from then on.  The labels are
+ * thresholded at every step, so the outline drifts over long clips: re-anchor
+ * with a keyframe.  smooth = 1 rounds corners (a 14 x 18 rectangle loses its 4
+ * corner pixels).  One object per call.  No scale, batch or stream variant.
+ */
+#define OF_MASK_CARRIED 0
+#define OF_MASK_VOTED 1
+#define OF_MASK_UNKNOWN 2
+#define OF_MASK_GIVEN 3
+#define OF_MASK_MAX_VOTE_RADIUS 12
+#define OF_MASK_MAX_SMOOTH 2
+typedef struct of_mask_opts {
+  int32_t vote_radius;   /* R of the vote's window, 1..12 (8) */
+  int32_t smooth;        /* s of the mode filter, 0..2 (1) */
+  double range;          /* the vote's colour range on the frames' value scale, like of_upsample_opts; finite, > 0 (20) */
+  double alpha1, alpha2; /* session only: forward-backward test, as of_fb_consistency; >= 0 */
+} of_mask_opts;
+/*
+ *   prev_mask  : H x W bytes
+ *   guide      : H x W x C, C 1..4
+ *   flow       : 2 x H x W, current -> previous
+ *   state      : H x W bytes, or NULL
+ *   out_mask   : H x W bytes, 0 / 1
+ *   out_status : H x W bytes, or NULL
+ */
+int of_mask_advance(of_ctx *ctx, const uint8_t *prev_mask, const float *guide, int H, int W, int C, const float *flow,
+                    const uint8_t *state, const of_mask_opts *opts, uint8_t *out_mask, uint8_t *out_status);
+/*
+ * The mask propagator session: one per context, beside the other kinds.  It
+ * keeps the previous frame and the current mask on the device; its buffers
+ * count in OF_OPT_DEVICE_BYTES from open to close, and of_ctx_destroy closes
+ * it.  C is 1 or 3.  A push with a mask (the first frame, or a re-anchor
+ * later) stores mask != 0, returns it with status OF_MASK_GIVEN everywhere and
+ * estimates nothing; the first push without a mask is OF_EINVAL.  A push
+ * without a mask estimates the pair (previous, this) in both directions at full
+ * resolution from zero flows with a fresh copy of the open's params and
+ * advances the stored mask along the backward flow with its state: bitwise
+ *   fw, bw, state_fw, state_bw = of_estimate_flow_bidir(previous, this; alpha1, alpha2)
+ *   out_mask, out_status = of_mask_advance(mask, this, bw, state_bw)
+ * out_mask: H x W bytes; out_status: H x W bytes or NULL.  A second open is
+ * refused (OF_EINVAL).  It is not a kind of_session_set_flow_scale takes: its
+ * pairs are estimated at full resolution.
+ */
+int of_masks_open(of_ctx *ctx, const of_params *params, int H, int W, int C, const of_mask_opts *opts);
+int of_masks_push(of_ctx *ctx, const float *frame, const uint8_t *mask, uint8_t *out_mask, uint8_t *out_status);
+int of_masks_close(of_ctx *ctx);
 
 /*
  * Layered motion segmentation.  of_fit_motion finds one motion, the dominant

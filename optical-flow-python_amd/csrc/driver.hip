@@ -25,6 +25,7 @@
 //   kernels_upsample.hip reduced-resolution flow: the box reduction of a frame, the edge-aware upsampling of a flow
 //   kernels_sr.hip     multi-frame super-resolution: the resampling along the flows, the back-projection step
 //   kernels_inpaint.hip flow-guided video inpainting: mask growing and the pair weight, the fill along the flows
+//   kernels_mask.hip   mask propagation: the carry along the backward flow, the colour-guided vote, the mode filter
 //   kernels_motion.hip global motion: the passes of the robust parametric fit, the affine warp
 //   kernels_layers.hip layered motion segmentation (uses the fit's passes)
 //   kernels_solve.hip  what the solvers share (partials, fixed-order sums, residual), norm and residual diagnostics
@@ -47,6 +48,7 @@
 //   host_fuse.hip   temporal denoising: flow composition, frame fusion, stage entries, the rings of frames and pairs, the session and its automatic sigma
 //   host_sr.hip     multi-frame super-resolution: the resampling and back-projection, the stage entry, the session
 //   host_inpaint.hip flow-guided video inpainting: mask growing, the fill, the stage entries, the session with its weighted pairs
+//   host_mask.hip   mask propagation: one step, the stage entry, the session
 //   host_motion.hip global motion: the robust parametric fit, the affine warp, path smoothing, the stabiliser session
 //   host_layers.hip layered motion segmentation: hypotheses, extraction, joint rounds, the stage entry
 //   batch.hip       lanes, of_pairs_run[_host], pair pool, slot copies, RCCL gather
@@ -82,6 +84,7 @@
 #include "kernels_upsample.hip"
 #include "kernels_sr.hip"
 #include "kernels_inpaint.hip"
+#include "kernels_mask.hip"
 #include "kernels_motion.hip"
 #include "kernels_layers.hip"
 #include "kernels_solve.hip"
@@ -102,6 +105,7 @@
 #include "host_fuse.hip"
 #include "host_sr.hip"
 #include "host_inpaint.hip"
+#include "host_mask.hip"
 #include "host_motion.hip"
 #include "host_layers.hip"
 #include "batch.hip"

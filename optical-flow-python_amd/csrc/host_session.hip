@@ -1,5 +1,6 @@
 // host_session.hip — what the frame-sequence sessions of a context (point
-// tracker, temporal denoiser, stabiliser, super-resolver, inpainter: Session, host_core.h) share: the
+// tracker, temporal denoiser, stabiliser, super-resolver, inpainter, mask
+// propagator: Session, host_core.h) share: the
 // words of their messages, lookup and free, the open and push prologues, the
 // bookkeeping of the delayed emitters and the switch to reduced-resolution
 // pairs (of_session_set_flow_scale).
@@ -13,7 +14,8 @@ const SessionKind SESSION_KIND[SES_KINDS] = {{"point tracker", "of_tracks_", "po
                                              {"temporal denoiser", "of_denoise_", "temporal fusion"},
                                              {"stabiliser", "of_stab_", "global motion"},
                                              {"super-resolver", "of_sr_", "super-resolution"},
-                                             {"inpainter", "of_inpaint_", "video inpainting"}};
+                                             {"inpainter", "of_inpaint_", "video inpainting"},
+                                             {"mask propagator", "of_masks_", "mask propagation"}};
 
 std::string session_not_open(int kind) {
   const SessionKind &K = SESSION_KIND[kind];

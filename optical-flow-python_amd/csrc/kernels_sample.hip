@@ -5,8 +5,8 @@
 // contraction, one fixed order of operations, so a numpy float64 restatement
 // gives the same bits.  Device functions only, no kernel; expects nothing
 // before it but kernels.h.  Used by kernels_interp.hip, kernels_track.hip,
-// kernels_fuse.hip, kernels_noise.hip, kernels_sr.hip, kernels_inpaint.hip
-// and kernels_motion.hip, all included after this file.
+// kernels_fuse.hip, kernels_noise.hip, kernels_sr.hip, kernels_inpaint.hip,
+// kernels_mask.hip and kernels_motion.hip, all included after this file.
 #include "kernels.h"
 
 // the four taps and two fractions of the clamped bilinear sample at (r, q),

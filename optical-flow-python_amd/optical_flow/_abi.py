@@ -222,6 +222,17 @@ class OfInpaintOpts(C.Structure):
     _fields_ = [("radius", C.c_int32), ("grow", C.c_int32), ("margin", C.c_int32), ("pad_", C.c_int32)]
 
 
+# mask propagation (include/optflow.h, "Mask propagation"): status bytes and ranges
+OF_MASK_CARRIED, OF_MASK_VOTED, OF_MASK_UNKNOWN, OF_MASK_GIVEN = 0, 1, 2, 3
+MASK_MAX_VOTE_RADIUS, MASK_MAX_SMOOTH = 12, 2
+MASK_MAX_CHANNELS = 4
+
+
+class OfMaskOpts(C.Structure):
+    _fields_ = [("vote_radius", C.c_int32), ("smooth", C.c_int32), ("range", C.c_double), ("alpha1", C.c_double),
+                ("alpha2", C.c_double)]
+
+
 def penalty(kind, p0=1.0, p1=0.0):
     return OfPenalty(PENALTY[kind], 0, float(p0), float(p1))
 

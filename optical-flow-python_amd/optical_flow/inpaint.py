@@ -1,6 +1,7 @@
-"""Flow-guided video inpainting (object removal): the caller marks a region in
-every frame of a clip, and the region is filled with what the other frames show
-there, carried along the motion.  Under the marks the flows are completed from
+"""Flow-guided video inpainting (object removal): a region is marked in every
+frame of a clip (masks.propagate_masks makes those masks from one drawn mask),
+and the region is filled with what the other frames show there, carried along
+the motion.  Under the marks the flows are completed from
 their surroundings by the solver (a data weight of 0, pair_weight); a marked
 pixel then walks through the completed flows of the adjacent pairs, forward and
 backward, until it lands on a pixel that some frame really saw
