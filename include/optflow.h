@@ -1161,10 +1161,12 @@ int of_sr_close(of_ctx *ctx);
  * hits it moves only through grown holes, where that test says nothing, and the
  * hit itself uses no flow.
  *
- * Known limits: no spatial fallback (a pixel that no frame within `radius`
- * reveals comes back OF_INPAINT_UNFILLED), no seam or exposure blending; a hole
- * bordered by two motions gets the smoothness term's blend of them; the marks
- * must cover shadows and reflections themselves, `grow` only pads them.
+ * Known limits: this fill has no spatial fallback (a pixel that no frame
+ * within `radius` reveals comes back OF_INPAINT_UNFILLED) and no seam or
+ * exposure blending: both are "Gradient-domain blending" below
+ * (of_inpaint_blend, of_inpaint_set_blend).  A hole bordered by two motions
+ * gets the smoothness term's blend of them; the marks must cover shadows and
+ * reflections themselves, `grow` only pads them.
  */
 #define OF_INPAINT_KEPT 0
 #define OF_INPAINT_FILLED 1
@@ -1221,6 +1223,120 @@ int of_inpaint_push(of_ctx *ctx, const float *frame, const uint8_t *mask, float 
                     int32_t *out_index);
 int of_inpaint_flush(of_ctx *ctx, float *out, uint8_t *out_status, int32_t *out_index);
 int of_inpaint_close(of_ctx *ctx);
+
+/*
+ * Gradient-domain blending and the spatial fallback of the inpainter: a
+ * Poisson solve over the hole (Perez et al. 2003, as in Huang et al. 2016 and
+ * Xu et al. 2019).  The propagated colours supply the gradients and the
+ * frame's own pixels around the hole the boundary values, so an exposure
+ * offset of a source frame is spread through the hole instead of sitting at
+ * its rim; where no colour was propagated the gradients are zero and the same
+ * solve gives a smooth membrane.  Everything in double from the fp32 or byte
+ * inputs, no fma contraction, in exactly the order written (a numpy float64
+ * restatement gives the same bits).  H * W >= 2^31: OF_ENOTSUP.  Any option out
+ * of range: OF_EINVAL, checked on the host before any launch.
+ *
+ * The linear problem, per channel on an H x W frame: a label plane (OF_PSN_FIXED,
+ * OF_PSN_UNKNOWN, OF_PSN_EXCLUDED), a value plane v (the Dirichlet data where
+ * fixed, the start value where unknown), a source plane s and a byte plane h
+ * ("has a source"; both may be NULL: no guidance).  For an unknown p, N(p) is
+ * its 4-neighbours inside the frame that are not excluded, in the order up,
+ * down, left, right, and deg = |N(p)|:
+ *   deg x_p - sum_{n in N(p), unknown} x_n = g_p + f_p
+ *   g = 0.0; for n in N(p) with h_p and h_n:  g = g + (s_p - s_n)
+ *   f = 0.0; for n in N(p), fixed:            f = f + v_n
+ *   b_p = g + f
+ * deg = 0: x_p = v_p; fixed and excluded pixels come back as v.
+ *
+ * The solver is a fixed multigrid schedule of elementwise steps: no reduction,
+ * no stopping test, so it depends on (H, W, options) alone and its result is
+ * a function of the inputs to the bit.  A component of unknowns without a
+ * fixed neighbour is singular and gets no special case: what the schedule
+ * makes of the start values is the result.
+ *   Levels.  Level l has ceil(H / 2^l) x ceil(W / 2^l) cells, cell (I, J) of
+ *   level l+1 covering cells 2I, 2I+1 x 2J, 2J+1 of level l (anchored at the
+ *   frame's origin, cells outside the frame excluded); L is the first level
+ *   with (rows + 2) * (columns + 2) <= 1024.  A cell has an integer diagonal d
+ *   (0: not solved for) and integer weights w towards up, down, left, right.
+ *   Level 0: d = deg on the unknown pixels, w = 1 towards an unknown
+ *   neighbour.  Level l+1, the Galerkin operator of piecewise-constant
+ *   transfer, from the children c00 c01 / c10 c11:
+ *     up = up(c00) + up(c01); down = down(c10) + down(c11)
+ *     left = left(c00) + left(c10); right = right(c01) + right(c11)
+ *     d = d(c00) + d(c01) + d(c10) + d(c11)
+ *         - 2 (right(c00) + right(c10) + down(c00) + down(c01))
+ *   Sweep (red-black Gauss-Seidel).  For colour k = 0, then 1, every cell with
+ *   d > 0 and (row + column) & 1 == k at once:
+ *     t = b; for n = up, down, left, right with w_n != 0: t = t + (double)w_n * x_n
+ *     x = t / (double)d
+ *   Residual of a cell with d > 0 (0.0 elsewhere):
+ *     r = b - (double)d * x; for n as above: r = r + (double)w_n * x_n
+ *   cycle(l), l < L: `sweeps` sweeps; the next level's b = ((r(c00) + r(c01)) +
+ *   r(c10)) + r(c11) where its d > 0, else 0.0, and its x = 0.0; cycle(l+1),
+ *   and once more when l + 1 < L (a W-cycle); x = x + 1.5 * x_parent on the
+ *   cells with d > 0 (1.5: the Galerkin correction of piecewise-constant
+ *   transfer undershoots smooth errors by about half; measured in
+ *   DESIGN.md); `sweeps` sweeps.  cycle(L): `coarse_sweeps` sweeps.
+ *   The solve: x = v, then `cycles` times cycle(0).
+ * The library works on a window around the unknowns only; cells without an
+ * unknown change nothing, so the window is invisible in the result.
+ *
+ * Blended fill of frame t (of_inpaint_blend; inputs as of_inpaint_fill).  (s, st)
+ * = of_inpaint_fill of frame t with grow + 1 (a propagated colour on the
+ * one-pixel ring around the hole as well: the boundary gradients), h = (st ==
+ * OF_INPAINT_FILLED), Om = grow(M_t, grow), I the frame.
+ *   Stage 1: unknown = Om & h, excluded = Om & !h, fixed elsewhere with value
+ *            I; start s; guidance (s, h).
+ *   Stage 2: unknown = Om & !h, everything else fixed at stage 1's result (in
+ *            double); start I; no guidance.  Skipped when Om is empty; where
+ *            Om & !h is empty it changes nothing.
+ *   out = (float) of the result on Om, I elsewhere; status OF_INPAINT_KEPT
+ *   outside Om, OF_INPAINT_FILLED on Om & h, OF_INPAINT_SPATIAL on Om & !h;
+ *   OF_INPAINT_UNFILLED never appears.
+ *
+ * Known limits: the membrane is smooth, no texture is synthesised; a gain
+ * change scales the copied gradients and is only partly corrected (on the
+ * tests' scene with 3 % per frame, a mean squared error of 120 becomes 24);
+ * colours from different source frames meet inside the hole with their
+ * gradient seams left as they are; a region that touches a single fixed pixel
+ * converges slowly (the coarsest level is relaxed, not solved).
+ */
+#define OF_INPAINT_SPATIAL 3
+#define OF_PSN_FIXED 0
+#define OF_PSN_UNKNOWN 1
+#define OF_PSN_EXCLUDED 2
+#define OF_BLEND_MAX_CYCLES 64
+#define OF_BLEND_MAX_SWEEPS 2
+#define OF_BLEND_MAX_COARSE_SWEEPS 64
+typedef struct of_blend_opts {
+  int32_t cycles;         /* W-cycles of a solve, 1..64 (8) */
+  int32_t sweeps;         /* red-black sweeps before and after the coarse correction, 1..2 (2) */
+  int32_t coarse_sweeps;  /* sweeps of the coarsest level per visit, 1..64 (32) */
+  int32_t pad_;
+} of_blend_opts;
+/*
+ *   label      : H x W bytes, OF_PSN_* (anything else: OF_EINVAL)
+ *   values     : H x W x C interleaved, C 1..4
+ *   source     : H x W x C, or NULL
+ *   has_source : H x W bytes (nonzero = has a source), NULL exactly when source is
+ *   out        : H x W x C doubles
+ */
+int of_poisson_solve(of_ctx *ctx, const uint8_t *label, const float *values, const float *source,
+                     const uint8_t *has_source, int H, int W, int C, const of_blend_opts *opts, double *out);
+/* arguments as of_inpaint_fill, without the hop counts */
+int of_inpaint_blend(of_ctx *ctx, const float *frames, const uint8_t *masks, const float *fw, const float *bw, int T,
+                     int H, int W, int C, int t, const of_inpaint_opts *opts, const of_blend_opts *blend, float *out,
+                     uint8_t *out_status);
+/*
+ * Blending in the inpainter session: valid after of_inpaint_open and before
+ * the first push, otherwise OF_EINVAL; NULL turns it off again.  With it set
+ * every emitted frame is of_inpaint_blend of that frame instead of
+ * of_inpaint_fill; the masks grown by one more are kept beside the ring's and
+ * count in OF_OPT_DEVICE_BYTES from this call to the close, the solver's
+ * buffers come from the context's grow-only arena.  Without it the pushes are
+ * bitwise what they are without this call.
+ */
+int of_inpaint_set_blend(of_ctx *ctx, const of_blend_opts *blend);
 
 /*
  * Mask propagation: a marked object followed through a clip.  The binary mask

@@ -25,6 +25,7 @@
 //   kernels_upsample.hip reduced-resolution flow: the box reduction of a frame, the edge-aware upsampling of a flow
 //   kernels_sr.hip     multi-frame super-resolution: the resampling along the flows, the back-projection step
 //   kernels_inpaint.hip flow-guided video inpainting: mask growing and the pair weight, the fill along the flows
+//   kernels_poisson.hip gradient-domain blending: the multilevel Poisson solver's steps, the blended fill's label planes and result
 //   kernels_mask.hip   mask propagation: the carry along the backward flow, the colour-guided vote, the mode filter
 //   kernels_motion.hip global motion: the passes of the robust parametric fit, the affine warp
 //   kernels_layers.hip layered motion segmentation (uses the fit's passes)
@@ -47,7 +48,8 @@
 //   host_noise.hip  noise-level estimation: the pair and single-frame estimators, their stage entries
 //   host_fuse.hip   temporal denoising: flow composition, frame fusion, stage entries, the rings of frames and pairs, the session and its automatic sigma
 //   host_sr.hip     multi-frame super-resolution: the resampling and back-projection, the stage entry, the session
-//   host_inpaint.hip flow-guided video inpainting: mask growing, the fill, the stage entries, the session with its weighted pairs
+//   host_poisson.hip the multilevel Poisson solver: levels and windows, setup, the W-cycle schedule, the stage entry
+//   host_inpaint.hip flow-guided video inpainting: mask growing, the fill, the blended fill, the stage entries, the session with its weighted pairs
 //   host_mask.hip   mask propagation: one step, the stage entry, the session
 //   host_motion.hip global motion: the robust parametric fit, the affine warp, path smoothing, the stabiliser session
 //   host_layers.hip layered motion segmentation: hypotheses, extraction, joint rounds, the stage entry
@@ -84,6 +86,7 @@
 #include "kernels_upsample.hip"
 #include "kernels_sr.hip"
 #include "kernels_inpaint.hip"
+#include "kernels_poisson.hip"
 #include "kernels_mask.hip"
 #include "kernels_motion.hip"
 #include "kernels_layers.hip"
@@ -104,6 +107,7 @@
 #include "host_noise.hip"
 #include "host_fuse.hip"
 #include "host_sr.hip"
+#include "host_poisson.hip"
 #include "host_inpaint.hip"
 #include "host_mask.hip"
 #include "host_motion.hip"

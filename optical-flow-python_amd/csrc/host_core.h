@@ -230,6 +230,13 @@ struct SuperResolver : PairRing {
   of_sr_opts opt;
 };
 
+// rows ilo .. ihi and columns jlo .. jhi of a frame, inclusive; empty when ihi < ilo
+// (the bounding box the Poisson solver's window is built around, host_poisson.hip)
+struct PsnBox {
+  int ilo = 0, ihi = -1, jlo = 0, jhi = -1;
+  bool empty() const { return ihi < ilo || jhi < jlo; }
+};
+
 // the inpainter (of_inpaint_open, host_inpaint.hip): rings of 2R+1 frames and
 // grown masks and of the last 2R adjacent pairs' flows, R up to 16
 struct Inpainter : Session {
@@ -237,6 +244,11 @@ struct Inpainter : Session {
   int pitch = 0;
   std::vector<uint8_t *> mask;     // the grown mask of frame k at k % (2R+1): H x W dense
   std::vector<float2 *> fw, bw;    // pair (j, j+1) at j % 2R: pitched flows j -> j+1 and j+1 -> j
+  // of_inpaint_set_blend: every emitted frame is the blended fill
+  bool blend = false;
+  of_blend_opts bopt = {};
+  std::vector<uint8_t *> mask1;    // the masks grown by one more, like `mask`
+  std::vector<PsnBox> box;         // the grown mask's bounding box, taken on the host at the push, like `mask`
 };
 
 // the mask propagator (of_masks_open, host_mask.hip): a ring of 2 frames and

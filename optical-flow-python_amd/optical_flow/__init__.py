@@ -12,7 +12,8 @@ from optical_flow.tracking import (advance_points, seed_points, PointTracker, tr
 from optical_flow.temporal import compose_flows, fuse_frames, fuse_weights, TemporalDenoiser, denoise_frames
 from optical_flow.superres import super_resolve, SuperResolver, super_resolve_frames
 from optical_flow.inpaint import (grow_mask, pair_weight, propagate_fill, VideoInpainter, inpaint_frames,
-                                  INPAINT_KEPT, INPAINT_FILLED, INPAINT_UNFILLED)
+                                  INPAINT_KEPT, INPAINT_FILLED, INPAINT_UNFILLED, poisson_fill, blend_fill,
+                                  INPAINT_SPATIAL)
 from optical_flow.masks import (advance_mask, MaskPropagator, propagate_masks, MASK_CARRIED, MASK_VOTED, MASK_UNKNOWN,
                                 MASK_GIVEN)
 from optical_flow.noise import estimate_noise, NoiseEstimate
@@ -38,4 +39,4 @@ __all__ = ['estimate_flow', 'estimate_flow_batch', 'PairStream', 'read_flo', 'wr
            'reduce_frame', 'upsample_flow', 'fuse_weights', 'super_resolve', 'SuperResolver', 'super_resolve_frames',
            'grow_mask', 'pair_weight', 'propagate_fill', 'VideoInpainter', 'inpaint_frames', 'INPAINT_KEPT',
            'INPAINT_FILLED', 'INPAINT_UNFILLED', 'advance_mask', 'MaskPropagator', 'propagate_masks', 'MASK_CARRIED',
-           'MASK_VOTED', 'MASK_UNKNOWN', 'MASK_GIVEN']
+           'MASK_VOTED', 'MASK_UNKNOWN', 'MASK_GIVEN', 'poisson_fill', 'blend_fill', 'INPAINT_SPATIAL']

@@ -222,6 +222,17 @@ class OfInpaintOpts(C.Structure):
     _fields_ = [("radius", C.c_int32), ("grow", C.c_int32), ("margin", C.c_int32), ("pad_", C.c_int32)]
 
 
+# gradient-domain blending (include/optflow.h, "Gradient-domain blending"): the status byte, labels and ranges
+OF_INPAINT_SPATIAL = 3
+OF_PSN_FIXED, OF_PSN_UNKNOWN, OF_PSN_EXCLUDED = 0, 1, 2
+BLEND_MAX_CYCLES, BLEND_MAX_SWEEPS, BLEND_MAX_COARSE_SWEEPS = 64, 2, 64
+BLEND_MAX_CHANNELS = 4
+
+
+class OfBlendOpts(C.Structure):
+    _fields_ = [("cycles", C.c_int32), ("sweeps", C.c_int32), ("coarse_sweeps", C.c_int32), ("pad_", C.c_int32)]
+
+
 # mask propagation (include/optflow.h, "Mask propagation"): status bytes and ranges
 OF_MASK_CARRIED, OF_MASK_VOTED, OF_MASK_UNKNOWN, OF_MASK_GIVEN = 0, 1, 2, 3
 MASK_MAX_VOTE_RADIUS, MASK_MAX_SMOOTH = 12, 2
