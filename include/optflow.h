@@ -1701,6 +1701,33 @@ int of_detect_occlusion(of_ctx *ctx, const float *uv, const float *images, int H
 /* denoise_color_weighted_medfilt2 (utils/weighted_median.py:24-112) */
 int of_weighted_median(of_ctx *ctx, const float *uv, const float *guide, int gc, const float *occ,
                        int H, int W, int area_hsz, double sigma_i, float *out);
+/* of_weighted_median with the warping loop's fused duv bookkeeping
+ * (classic_nl.py:271-275): base == NULL is of_weighted_median; otherwise
+ * out = base + (median - base) in float32, computed in the filter's own store
+ * with the result written over the base's buffer, as a Classic+NL warp does. */
+int of_weighted_median_base(of_ctx *ctx, const float *uv, const float *guide, int gc, const float *occ,
+                            int H, int W, int area_hsz, double sigma_i, const float *base, float *out);
+/* ---- stage entries of one level's warping loop (parity tests) ----
+ * Each runs exactly the host function of_compute_flow_base runs.
+ *
+ * of_warp_operator: the fused warp + assembly, the default linearisation of
+ * every method but AltBA: the level's derivative planes of `images` (planar
+ * 2*nc, interpolation and derivative filter of `params`, `blend` as
+ * of_partial_deriv) and then coef / rhs of of_flow_operator_weighted at `uv`
+ * with no duv, bitwise what of_partial_deriv + of_flow_operator_weighted
+ * give.  weight: H x W or NULL.  OF_ENOTSUP where the level would not fuse:
+ * nc not 1 or 3, AltBA, or OF_OPT_FUSED_WARP off. */
+int of_warp_operator(of_ctx *ctx, const of_params *params, double alpha, const float *images, int H, int W,
+                     int nc, const float *uv, const float *weight, double blend, float *coef, float *rhs);
+/* The IRLS update (classic_nl.py:250-262): out_uv1 = uv + clip(x), clip to
+ * [-1, 1] when `clip` is non-zero, one float32 rounding; with out_occ also
+ * detect_occlusion(out_uv1, images) (utils/occlusion.py:6-56) from the same
+ * launch.  images (planar 2*nc) may be NULL when out_occ is. */
+int of_flow_update(of_ctx *ctx, const float *uv, const float *x, int clip, const float *images, int H, int W,
+                   int nc, float *out_uv1, float *out_occ);
+/* scipy.ndimage.median_filter(size, mode='reflect') of both components of a
+ * flow field at once (hs.py:137-140, ba.py:197-199); size 3, 5 or 7 */
+int of_median_filter_flow(of_ctx *ctx, const float *uv, int H, int W, int size, float *out);
 /* flow_to_color (viz/flow_color.py:77-107): Middlebury colour coding of an
  * interleaved (H, W, 2) flow of dtype 0 = float32 or 1 = float64 into an
  * (H, W, 3) uint8 image; |u| or |v| > 1e9 is unknown (black).  has_max = 0

@@ -659,13 +659,77 @@ int of_detect_occlusion(of_ctx *c, const float *uv, const float *images, int H, 
   API_END(c)
 }
 
-int of_weighted_median(of_ctx *c, const float *uv, const float *guide, int gc, const float *occ, int H, int W,
-                       int area_hsz, double sigma_i, float *out) {
+int of_weighted_median_base(of_ctx *c, const float *uv, const float *guide, int gc, const float *occ, int H, int W,
+                            int area_hsz, double sigma_i, const float *base, float *out) {
   API_BEGIN(c)
   REQUIRE(uv && guide && occ && out && gc >= 1, OF_EINVAL, "bad arguments");
-  F2 f = upload_f2(c, uv, H, W), o = new_f2(c, H, W);
+  F2 f = upload_f2(c, uv, H, W), o;
   Img g = upload_new_img(c, guide, H, W, gc), oc = upload_new_img(c, occ, H, W, 1);
-  wmf(c, f, g, oc.p, o, area_hsz, sigma_i);
+  // with a base the store goes to the base's own buffer, as irls_base has it
+  if (base) o = upload_f2(c, base, H, W);
+  else o = new_f2(c, H, W);
+  wmf(c, f, g, oc.p, o, area_hsz, sigma_i, base ? (const float2 *)o.p : nullptr);
+  download_f2(c, o, out);
+  HIPCHK(hipStreamSynchronize(c->stream));
+  API_END(c)
+}
+
+int of_weighted_median(of_ctx *c, const float *uv, const float *guide, int gc, const float *occ, int H, int W,
+                       int area_hsz, double sigma_i, float *out) {
+  return of_weighted_median_base(c, uv, guide, gc, occ, H, W, area_hsz, sigma_i, nullptr, out);
+}
+
+// level_deriv + warp_operator, as hs_base / irls_base run them on a level
+int of_warp_operator(of_ctx *c, const of_params *P, double alpha, const float *images, int H, int W, int nc,
+                     const float *uv, const float *weight, double blend, float *coef, float *rhs) {
+  API_BEGIN(c)
+  REQUIRE(P && images && uv && coef && rhs && nc >= 1 && nc <= OF_MAX_NC, OF_EINVAL, "bad arguments");
+  REQUIRE(P->interp >= 0 && P->interp <= 2, OF_EINVAL, "Unknown interpolation method");
+  const OpArgs o = op_args(P, alpha, 0.0);
+  REQUIRE(can_fuse_warp_op(c, o, nc), OF_ENOTSUP,
+          "the fused warp + assembly takes 1 or 3 channels, not AltBA, with OF_OPT_FUSED_WARP on");
+  const Img wgt = upload_weight(c, P, weight, H, W);
+  Img im = upload_new_img(c, images, H, W, 2 * nc);
+  F2 f = upload_f2(c, uv, H, W);
+  c->cur_px = (double)H * W;
+  LevelDeriv D = level_deriv(c, im, nc, P->interp, P->deriv_filter, blend);
+  Img cf = new_img(c, H, W, 7);
+  F2 r = new_f2(c, H, W);
+  warp_operator(c, D, P->interp, o, f, cf, r, wgt);
+  download_img(c, cf, coef);
+  download_f2(c, r, rhs);
+  HIPCHK(hipStreamSynchronize(c->stream));
+  API_END(c)
+}
+
+// k_update_occ as irls_base launches it: out_uv1 = uv + clip(x) and, with
+// out_occ, detect_occlusion of that field
+int of_flow_update(of_ctx *c, const float *uv, const float *x, int clip, const float *images, int H, int W, int nc,
+                   float *out_uv1, float *out_occ) {
+  API_BEGIN(c)
+  REQUIRE(uv && x && out_uv1 && (!out_occ || (images && nc >= 1 && nc <= OF_MAX_NC)), OF_EINVAL, "bad arguments");
+  F2 f = upload_f2(c, uv, H, W), dx = upload_f2(c, x, H, W), u1 = new_f2(c, H, W);
+  Img im, o;
+  if (images) im = upload_new_img(c, images, H, W, 2 * nc);
+  if (out_occ) o = new_img(c, H, W, 1);
+  c->cur_px = (double)H * W;
+  Grid2 g = grid2(H, W);
+  launch(c, out_occ ? "update_occ" : "update", k_update_occ, g.grid, g.block, 0, (const float2 *)f.p,
+         (const float2 *)dx.p, clip ? 1 : 0, u1.p, (const float *)im.p,
+         (const float *)(images ? im.plane(nc) : nullptr), nc, o.p, H, W, f.P, images ? im.ps() : (size_t)0);
+  download_f2(c, u1, out_uv1);
+  if (out_occ) download_img(c, o, out_occ);
+  HIPCHK(hipStreamSynchronize(c->stream));
+  API_END(c)
+}
+
+// median2(): the float2 median of hs_base / irls_base (k_median2<size>)
+int of_median_filter_flow(of_ctx *c, const float *uv, int H, int W, int size, float *out) {
+  API_BEGIN(c)
+  REQUIRE(uv && out, OF_EINVAL, "bad arguments");
+  F2 f = upload_f2(c, uv, H, W), o = new_f2(c, H, W);
+  c->cur_px = (double)H * W;
+  median2(c, f, o, size);
   download_f2(c, o, out);
   HIPCHK(hipStreamSynchronize(c->stream));
   API_END(c)

@@ -146,6 +146,12 @@ _SIGS = {
     "of_solve_dia": ([_vp, C.POINTER(OfParams), C.c_int, _fp, _fp, C.c_int, C.c_int, _fp, _ip, _dp], C.c_int),
     "of_detect_occlusion": ([_vp, _fp, _fp, C.c_int, C.c_int, C.c_int, _fp], C.c_int),
     "of_weighted_median": ([_vp, _fp, _fp, C.c_int, _fp, C.c_int, C.c_int, C.c_int, C.c_double, _fp], C.c_int),
+    "of_weighted_median_base": ([_vp, _fp, _fp, C.c_int, _fp, C.c_int, C.c_int, C.c_int, C.c_double, _fp, _fp],
+                                C.c_int),
+    "of_warp_operator": ([_vp, C.POINTER(OfParams), C.c_double, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp,
+                          C.c_double, _fp, _fp], C.c_int),
+    "of_flow_update": ([_vp, _fp, _fp, C.c_int, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp], C.c_int),
+    "of_median_filter_flow": ([_vp, _fp, C.c_int, C.c_int, C.c_int, _fp], C.c_int),
     "of_median_filter": ([_vp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp], C.c_int),
     "of_flow_to_color": ([_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, _vp], C.c_int),
     "of_solver_geometry": ([C.c_int, C.c_int, C.c_int, C.POINTER(OfCgGeometry)], C.c_int),

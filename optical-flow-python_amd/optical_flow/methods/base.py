@@ -342,6 +342,21 @@ class BaseOpticalFlow(ABC):
             nat.ptr(nat.planar(Ix)), nat.ptr(nat.planar(Iy)), H, W, nc, nat.ptr(coef), nat.ptr(rhs)))
         return coef, rhs
 
+    def _warp_operator_planes(self, uv, alpha, blend=0.5, data_weight=None):
+        """_operator_planes of partial_deriv(self.images, uv) with no duv from
+        the fused warp + assembly a level runs by default (of_warp_operator):
+        the same planes bit for bit, without the derivative planes."""
+        images, H, W, nc = self._images_planar()
+        wgt = nat.data_weight(data_weight, H, W)
+        P = self.to_params()
+        coef = np.empty((7, H, W), dtype=np.float32)
+        rhs = np.empty((2, H, W), dtype=np.float32)
+        ctx = nat.context()
+        ctx.check(ctx.lib.of_warp_operator(ctx.handle, C.byref(P), float(alpha), nat.ptr(images), H, W, nc,
+                                           nat.ptr(nat.planar(uv)), nat.ptr(wgt), float(blend), nat.ptr(coef),
+                                           nat.ptr(rhs)))
+        return coef, rhs
+
     def _operator_dia(self, uv, duv, It, Ix, Iy, alpha):
         uv = np.asarray(uv, dtype=float)
         H, W = uv.shape[:2]

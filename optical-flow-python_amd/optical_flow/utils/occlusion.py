@@ -19,6 +19,31 @@ def detect_occlusion(uv, images, sigma_d=0.3, sigma_i=20.0):
     return out.astype(float)
 
 
+def flow_update(uv, x, clip=True, images=None):
+    """The update of an IRLS warp as one level runs it (of_flow_update):
+    uv + clip(x, -1, 1) in float32 (clip=False: uv + x), and with `images`
+    also detect_occlusion of that field from the same launch.  Returns uv1,
+    or (uv1, occ) when images are given."""
+    uv = np.asarray(uv, dtype=float)
+    x = np.asarray(x, dtype=float)
+    if uv.ndim != 3 or uv.shape[2] != 2 or x.shape != uv.shape:
+        raise ValueError(f"uv and x must both be (H, W, 2), got {uv.shape} / {x.shape}")
+    H, W = uv.shape[:2]
+    out = np.empty((2, H, W), dtype=np.float32)
+    occ, im, nc = None, None, 0
+    if images is not None:
+        images = np.asarray(images, dtype=float)
+        if images.ndim != 3 or images.shape[:2] != (H, W) or images.shape[2] % 2:
+            raise ValueError(f"images must be ({H}, {W}, 2*nc), got {images.shape}")
+        im, nc = nat.planar(images), images.shape[2] // 2
+        occ = np.empty((H, W), dtype=np.float32)
+    ctx = nat.context()
+    ctx.check(ctx.lib.of_flow_update(ctx.handle, nat.ptr(nat.planar(uv)), nat.ptr(nat.planar(x)), int(bool(clip)),
+                                     nat.ptr(im), H, W, nc, nat.ptr(out), nat.ptr(occ)))
+    uv1 = nat.interleaved(out)
+    return uv1 if occ is None else (uv1, occ.astype(float))
+
+
 # states of forward_backward_check (of_fb_consistency, include/optflow.h)
 FB_CONSISTENT = 0
 FB_OCCLUDED = 1

@@ -25,12 +25,29 @@ def median_filter2(a, size):
     return out[0].astype(float) if a.ndim == 2 else nat.interleaved(out)
 
 
-def denoise_color_weighted_medfilt2(uv, color_images, occ, area_hsz, mfsz, sigma_i, full_version=False):
+def median_filter_flow(uv, size):
+    """median_filter2 of an (H, W, 2) flow field with both components in one
+    launch: the form a level's warping loop runs (of_median_filter_flow)."""
+    uv = np.asarray(uv, dtype=float)
+    H, W = uv.shape[:2]
+    out = np.empty((2, H, W), dtype=np.float32)
+    ctx = nat.context()
+    ctx.check(ctx.lib.of_median_filter_flow(ctx.handle, nat.ptr(nat.planar(uv)), H, W, int(size), nat.ptr(out)))
+    return nat.interleaved(out)
+
+
+def denoise_color_weighted_medfilt2(uv, color_images, occ, area_hsz, mfsz, sigma_i, full_version=False, *,
+                                    base=None):
     """Colour-guided, occlusion-weighted median over a (2*area_hsz+1)^2 window
-    (weighted_median.py:24-112); plain median when there is no guide."""
+    (weighted_median.py:24-112); plain median when there is no guide.  `base`
+    (an extension, guided filter only): return base + (median - base) in
+    float32 from the filter's own store, as a Classic+NL warp computes it
+    (of_weighted_median_base)."""
     uv = np.asarray(uv, dtype=float)
     H, W = uv.shape[:2]
     if color_images is None or np.asarray(color_images).size < H * W:
+        if base is not None:
+            raise NotImplementedError("base needs a colour guide")
         sz = int(mfsz[0]) if hasattr(mfsz, '__len__') else int(mfsz)
         return median_filter2(uv, sz)
     g = np.asarray(color_images, dtype=float)
@@ -39,6 +56,14 @@ def denoise_color_weighted_medfilt2(uv, color_images, occ, area_hsz, mfsz, sigma
     gp = nat.planar(g)
     out = np.empty((2, H, W), dtype=np.float32)
     ctx = nat.context()
-    ctx.check(ctx.lib.of_weighted_median(ctx.handle, nat.ptr(nat.planar(uv)), nat.ptr(gp), gp.shape[0],
-                                         nat.ptr(nat.f32(occ)), H, W, int(area_hsz), float(sigma_i), nat.ptr(out)))
+    if base is None:
+        ctx.check(ctx.lib.of_weighted_median(ctx.handle, nat.ptr(nat.planar(uv)), nat.ptr(gp), gp.shape[0],
+                                             nat.ptr(nat.f32(occ)), H, W, int(area_hsz), float(sigma_i),
+                                             nat.ptr(out)))
+    else:
+        if np.shape(base) != uv.shape:
+            raise ValueError(f"base must be {uv.shape}, got {np.shape(base)}")
+        ctx.check(ctx.lib.of_weighted_median_base(ctx.handle, nat.ptr(nat.planar(uv)), nat.ptr(gp), gp.shape[0],
+                                                  nat.ptr(nat.f32(occ)), H, W, int(area_hsz), float(sigma_i),
+                                                  nat.ptr(nat.planar(base)), nat.ptr(out)))
     return nat.interleaved(out)

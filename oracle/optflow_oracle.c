@@ -1006,6 +1006,20 @@ void ofr_alt_ba_flow_base(const of_params *P, const double *images, int H, int W
   altba_base(&d, &L, uv, uvhat, alpha, replacement);
 }
 
+/* compute_flow_base(uv) of HS, BA and Classic+NL on one level (hs.py:109-142,
+ * ba.py:140-206, classic_nl.py:200-277) with P->max_linear linearisations per
+ * warp; images planar 2*nc, guide planar gc or NULL (Classic+NL then takes the
+ * plain median), uv planar 2 x H x W, updated in place */
+int ofr_compute_flow_base(const of_params *P, const double *images, int H, int W, int nc, const double *guide,
+                          int gc, double alpha, double *uv) {
+  if (P->filters.general || P->method == OF_METHOD_ALT_BA) return OF_ENOTSUP;
+  drv_t d = {P, NULL, nc, guide ? gc : 0};
+  level_t L = {H, W, (double *)images, (double *)guide};
+  if (P->method == OF_METHOD_HS) hs_base(&d, &L, uv);
+  else irls_base(&d, &L, uv, alpha, P->max_linear);
+  return OF_OK;
+}
+
 /* compute_flow for all four methods.  images planar 2*nc (frame-1 channels
  * then frame-2 channels); guide planar gc or NULL; init_uv may be NULL.
  * P->alpha is updated to the final GNC alpha (restored for BA). */

@@ -41,6 +41,8 @@ def lib():
                                            C.c_int, C.c_int, _dp, _dp]
         _lib.ofr_alt_ba_flow_base.argtypes = [C.POINTER(_abi.OfParams), _dp, C.c_int, C.c_int, C.c_int, C.c_double,
                                               C.c_int, _dp, _dp]
+        _lib.ofr_compute_flow_base.argtypes = [C.POINTER(_abi.OfParams), _dp, C.c_int, C.c_int, C.c_int, _dp,
+                                               C.c_int, C.c_double, _dp]
         _lib.ofr_solve.argtypes = [C.POINTER(_abi.OfParams), _dp, _dp, C.c_int, C.c_int, _dp, _ip, _dp]
         _lib.ofr_num_threads.restype = C.c_int
         _lib.ofr_set_backslash_rtol.argtypes = [C.c_double]
@@ -280,6 +282,25 @@ def alt_ba_flow_base(ope, uv, uvhat):
     lib().ofr_alt_ba_flow_base(C.byref(P), _p(im), H, W, im.shape[0] // 2, C.c_double(float(ope.alpha)),
                                int(bool(ope.replacement)), _p(u), _p(uh))
     return unplanar(u, False), unplanar(uh, False)
+
+
+def compute_flow_base(ope, uv):
+    """compute_flow_base(uv) of an HS, BA or Classic+NL method object on one
+    level (hs.py:109-142, ba.py:140-206, classic_nl.py:200-277) with ope's
+    attribute bag, images, color_images and alpha."""
+    P = ope.to_params()
+    im = planar(ope.images)
+    H, W = im.shape[1:]
+    g, gc = None, 0
+    if ope._METHOD == 'classic_nl' and ope.color_images is not None:
+        g = planar(ope.color_images)
+        gc = g.shape[0]
+    u = planar(uv).copy()
+    rc = lib().ofr_compute_flow_base(C.byref(P), _p(im), H, W, im.shape[0] // 2, _p(g), gc,
+                                     C.c_double(float(ope.alpha)), _p(u))
+    if rc != 0:
+        raise NotImplementedError("the oracle's level covers HS, BA and Classic+NL with the default filter pair")
+    return unplanar(u, False)
 
 
 def estimate_flow(im1, im2, method='classic+nl-fast', params=None, solver=None):
