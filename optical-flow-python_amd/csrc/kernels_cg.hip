@@ -130,25 +130,42 @@ struct CgInv {
 template <bool BLOCK>
 __device__ __forceinline__ CgInv cg_inv(const CgCoef &c) {
   CgInv o;
+  if (BLOCK) {
+    // the 2x2 inverse where det > 1e-30 |a d| (explicit fma: the same
+    // rounding wherever the inverse is formed), else scalar Jacobi.  On an
+    // assembled operator every lane passes, so the fallback's reciprocals
+    // and selects sit behind a wave-uniform branch: lanes that pass get the
+    // same values either way
+    bool ok[2];
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+      const float a = c.a[e], cc = c.c[e], d = c.d[e];
+      const float det = __builtin_fmaf(a, d, -(cc * cc));
+      ok[e] = det > 1e-30f * fabsf(a * d);
+      const float inv = __builtin_amdgcn_rcpf(det);
+      o.ia[e] = d * inv;
+      o.id[e] = a * inv;
+      o.ic[e] = -cc * inv;
+    }
+    if (__builtin_amdgcn_ballot_w64(!(ok[0] && ok[1])) != 0) {
+#pragma unroll
+      for (int e = 0; e < 2; ++e) {
+        const float a = c.a[e], d = c.d[e];
+        const float ja = fabsf(a) > 1e-12f ? __builtin_amdgcn_rcpf(a) : 0.f;
+        const float jd = fabsf(d) > 1e-12f ? __builtin_amdgcn_rcpf(d) : 0.f;
+        o.ia[e] = ok[e] ? o.ia[e] : ja;
+        o.id[e] = ok[e] ? o.id[e] : jd;
+        o.ic[e] = ok[e] ? o.ic[e] : 0.f;
+      }
+    }
+    return o;
+  }
 #pragma unroll
   for (int e = 0; e < 2; ++e) {
-    const float a = c.a[e], cc = c.c[e], d = c.d[e];
     // scalar Jacobi, base.py:129-131: 1/diag where |diag| > 1e-12 else 0
-    float ia = fabsf(a) > 1e-12f ? __builtin_amdgcn_rcpf(a) : 0.f;
-    float id = fabsf(d) > 1e-12f ? __builtin_amdgcn_rcpf(d) : 0.f;
-    float ic = 0.f;
-    if (BLOCK) {
-      // explicit fma: the same rounding wherever the inverse is formed
-      const float det = __builtin_fmaf(a, d, -(cc * cc));
-      const bool ok = det > 1e-30f * fabsf(a * d);
-      const float inv = __builtin_amdgcn_rcpf(det);
-      ia = ok ? d * inv : ia;
-      id = ok ? a * inv : id;
-      ic = ok ? -cc * inv : 0.f;
-    }
-    o.ia[e] = ia;
-    o.ic[e] = ic;
-    o.id[e] = id;
+    o.ia[e] = fabsf(c.a[e]) > 1e-12f ? __builtin_amdgcn_rcpf(c.a[e]) : 0.f;
+    o.id[e] = fabsf(c.d[e]) > 1e-12f ? __builtin_amdgcn_rcpf(c.d[e]) : 0.f;
+    o.ic[e] = 0.f;
   }
   return o;
 }

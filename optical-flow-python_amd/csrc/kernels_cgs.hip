@@ -201,6 +201,11 @@ __device__ unsigned long long g_cgs_t[4][3];  // [role] {work, wait, waves}
 #define CGS_T1
 #endif
 
+template <int U>
+struct CgsStep {  // position of a row step in the 8-step trip (CGS_STEPS)
+  static constexpr int value = U;
+};
+
 template <bool FIRST, bool ODD>
 __global__ __launch_bounds__(256) void k_cgs(PcgArgs g, int k, int R, int nbands) {
   __shared__ double lds[64];
@@ -248,14 +253,27 @@ __global__ __launch_bounds__(256) void k_cgs(PcgArgs g, int k, int R, int nbands
   const int rb0 = band * R, rb1 = min(rb0 + R, H);
   const int r0 = flip ? H - rb1 : rb0, r1 = flip ? H - rb0 : rb1;
   const float c0 = g.poly[0], c1 = g.poly[1], c2 = g.poly[2], c3 = g.poly[3], c4 = g.poly[4], c5 = g.poly[5];
-  auto orow = [&](int t) { return (unsigned)(flip ? H - 1 - t : t); };
-  auto o4 = [&](int t) { return off4 + ((unsigned)t < (unsigned)H ? orow(t) * rowb4 : CG_ROW_OOB); };
-  auto o8 = [&](int t) { return off8 + ((unsigned)t < (unsigned)H ? orow(t) * rowb8 : CG_ROW_OOB); };
-  auto o4w = [&](int t) {
-    return flip ? off4 + ((unsigned)t < (unsigned)(H - 1) ? (unsigned)(H - 2 - t) * rowb4 : CG_ROW_OOB) : o4(t);
-  };
-  auto load_raw = [&](int t, CgRaw &c) {
-    const unsigned v = o4(t), vw = o4w(t);
+  // Row offsets are stepped, not multiplied out per row: virtual row t lies
+  // at byte rw8(t) = base8 + t step8 of a vector and rw4(t) of a coefficient
+  // plane, in unsigned arithmetic that wraps for the rows of a walk outside
+  // the image.  Each role keeps running values that advance by one step per
+  // row step (set before the walk; the multiplications below run only there).
+  // For the single-plane vectors (range H P 8 bytes) the wrapped offset of a
+  // row t < 0 is >= 2^32 - 20 row pitches and that of a row t >= H is >= the
+  // range, with or without CG_OOB of an out-of-image column on top, so the
+  // descriptor's range check alone returns 0 / drops the access, without
+  // memory traffic.  The seven coefficient planes share one descriptor (a row
+  // >= H of planes 0..5 is in range), so their offsets keep a validity select.
+  const unsigned step4 = flip ? 0u - rowb4 : rowb4, step8 = flip ? 0u - rowb8 : rowb8;
+  const unsigned base4 = flip ? (unsigned)(H - 1) * rowb4 : 0u, base8 = flip ? (unsigned)(H - 1) * rowb8 : 0u;
+  auto rw4 = [&](int t) { return base4 + (unsigned)t * step4; };
+  auto rw8 = [&](int t) { return base8 + (unsigned)t * step8; };
+  // wy of virtual row t: the plane row above when flipped (orig row H-2-t)
+  const unsigned wadj4 = flip ? rowb4 : 0u, Hw = (unsigned)(flip ? H - 1 : H);
+  // row t's coefficients; c4 = rw4(t)
+  auto load_raw = [&](int t, unsigned c4, CgRaw &c) {
+    const unsigned v = off4 + ((unsigned)t < (unsigned)H ? c4 : CG_ROW_OOB);
+    const unsigned vw = off4 + ((unsigned)t < Hw ? c4 - wadj4 : CG_ROW_OOB);
     c.wxu = cg_mask1<ODD>(cg_ld2(rc, v, 0), ok1);
     c.wyu = cg_mask1<ODD>(cg_ld2(rc, vw, ps4), ok1);
     c.wxv = cg_mask1<ODD>(cg_ld2(rc, v, 2 * ps4), ok1);
@@ -266,13 +284,21 @@ __global__ __launch_bounds__(256) void k_cgs(PcgArgs g, int k, int R, int nbands
   };
   // records are keyed by absolute row (rows >= r0 - 7 >= -7)
   auto rslot = [](int t) { return (t + 2 * CGS_NREC) % CGS_NREC; };
-  auto put_rec = [&](int t, const CgRaw &c) {
+  // inside the walk the slot of row n is a running counter (CGS_RS_NEXT) and
+  // that of row n - d follows by one subtraction and wrap (rsl): no division
+  auto rsl = [](int rs, int d) {
+    const int s = rs - d;
+    return s < 0 ? s + CGS_NREC : s;
+  };
+#define CGS_RS_NEXT(rs) rs = (rs) + 1 == CGS_NREC ? 0 : (rs) + 1
+  // put_rec / get_rec / get_wy take the slot
+  auto put_rec = [&](int slot, const CgRaw &c) {
     CgCoef cc;
     cc.a = c.a;
     cc.c = c.c;
     cc.d = c.d;
     const CgInv mi = cg_inv<true>(cc);
-    float4 *q = &ring[rslot(t)][0][lane];
+    float4 *q = &ring[slot][0][lane];
     q[0] = make_float4(c.wxu.x, c.wxv.x, c.wyu.x, c.wyv.x);
     q[64] = make_float4(c.wxu.y, c.wxv.y, c.wyu.y, c.wyv.y);
     q[128] = make_float4(mi.ia.x, mi.ic.x, mi.ic.x, mi.id.x);
@@ -288,8 +314,8 @@ __global__ __launch_bounds__(256) void k_cgs(PcgArgs g, int k, int R, int nbands
     r.mb[1] = cg_f2{mi.ic.y, mi.id.y};
     return r;
   };
-  auto get_rec = [&](int t) {
-    const float4 *q = &ring[rslot(t)][0][lane];
+  auto get_rec = [&](int slot) {
+    const float4 *q = &ring[slot][0][lane];
     const float4 a = q[0], b = q[64], c = q[128], d = q[192];
     CgRec r;
     r.wx[0] = cg_f2{a.x, a.y};
@@ -302,8 +328,8 @@ __global__ __launch_bounds__(256) void k_cgs(PcgArgs g, int k, int R, int nbands
     r.mb[1] = cg_f2{d.z, d.w};
     return r;
   };
-  auto get_wy = [&](int t, cg_f2 (&wu)[2]) {  // vertical weight pairs only
-    const float2 *q = reinterpret_cast<const float2 *>(&ring[rslot(t)][0][lane]);
+  auto get_wy = [&](int slot, cg_f2 (&wu)[2]) {  // vertical weight pairs only
+    const float2 *q = reinterpret_cast<const float2 *>(&ring[slot][0][lane]);
     const float2 a = q[1], b = q[129];
     wu[0] = cg_f2{a.x, a.y};
     wu[1] = cg_f2{b.x, b.y};
@@ -313,8 +339,11 @@ __global__ __launch_bounds__(256) void k_cgs(PcgArgs g, int k, int R, int nbands
     return cg_f4{v.x, v.y, v.z, v.w};
   };
   auto st4 = [&](float4 (&rg)[4][64], int t, cg_f4 v) { rg[t & 3][lane] = make_float4(v.x, v.y, v.z, v.w); };
-  auto load_po = [&](int t) { return FIRST ? cg_f4{0.f, 0.f, 0.f, 0.f} : cg_mask1<ODD>(cg_ld4(rpo, o8(t)), ok1); };
-  auto load_rin = [&](int t) { return cg_mask1<ODD>(cg_ld4(rin, o8(t)), ok1); };
+  // (c8 = rw8(row): out-of-image rows are refused by the range check, above)
+  auto load_po = [&](unsigned c8) {
+    return FIRST ? cg_f4{0.f, 0.f, 0.f, 0.f} : cg_mask1<ODD>(cg_ld4(rpo, off8 + c8), ok1);
+  };
+  auto load_rin = [&](unsigned c8) { return cg_mask1<ODD>(cg_ld4(rin, off8 + c8), ok1); };
   // x_lo = 0 in the launch after a residual replacement (xz, known after
   // the prologue; the preamble's x rows are then dropped)
   bool xz = false;
@@ -322,9 +351,10 @@ __global__ __launch_bounds__(256) void k_cgs(PcgArgs g, int k, int R, int nbands
   // offset that returns 0 without memory traffic.  A branch around the load
   // makes the count of memory operations behind an earlier load depend on
   // the path, and the wait before that load's use then covers this step's)
-  auto load_x = [&](int t) {
+  const unsigned nrb = (unsigned)(r1 - r0);  // rows of the band
+  auto load_x = [&](int t, unsigned c8) {
     if (FIRST) return cg_f4{0.f, 0.f, 0.f, 0.f};
-    return cg_mask1<ODD>(cg_ld4(rx, !xz && t >= r0 && t < r1 ? o8(t) : CG_OOB), ok1);
+    return cg_mask1<ODD>(cg_ld4(rx, off8 + (!xz && (unsigned)(t - r0) < nrb ? c8 : CG_ROW_OOB)), ok1);
   };
   const bool dm0 = out_lane && ok0, dm1 = out_lane && ok1;
   auto mdot = [&](cg_f4 a, cg_f4 b) {
@@ -352,21 +382,21 @@ __global__ __launch_bounds__(256) void k_cgs(PcgArgs g, int k, int R, int nbands
   CgRaw SG[CGS_SGN], SGp[2];
   cg_f4 PO[8], RI[CGS_RIN], PO2[CGS_W2N], XI[CGS_W2N];
   if (live && role == 0) {
-    load_raw(ns - 2, SGp[0]);
-    load_raw(ns - 1, SGp[1]);
+    load_raw(ns - 2, rw4(ns - 2), SGp[0]);
+    load_raw(ns - 1, rw4(ns - 1), SGp[1]);
 #pragma unroll
-    for (int m = 0; m < CGS_PF; ++m) load_raw(ns + m, SG[m]);
+    for (int m = 0; m < CGS_PF; ++m) load_raw(ns + m, rw4(ns + m), SG[m]);
     SG[CGS_SGN - 1] = SGp[1];  // raw row ns-1: stage A's D at the first step
 #pragma unroll
-    for (int m = -2; m < CGS_PF; ++m) PO[m & 7] = load_po(ns + m);
+    for (int m = -2; m < CGS_PF; ++m) PO[m & 7] = load_po(rw8(ns + m));
 #pragma unroll
-    for (int m = -1; m < CGS_PF - 1; ++m) RI[(m + 16) & (CGS_RIN - 1)] = load_rin(ns + m);
+    for (int m = -1; m < CGS_PF - 1; ++m) RI[(m + 16) & (CGS_RIN - 1)] = load_rin(rw8(ns + m));
   }
   if (live && role == 2) {
 #pragma unroll
     for (int m = -8; m < CGS_PF2 - 8; ++m) {
-      PO2[(m + 16) & (CGS_W2N - 1)] = load_po(ns + m);
-      XI[(m + 16) & (CGS_W2N - 1)] = load_x(ns + m);
+      PO2[(m + 16) & (CGS_W2N - 1)] = load_po(rw8(ns + m));
+      XI[(m + 16) & (CGS_W2N - 1)] = load_x(ns + m, rw8(ns + m));
     }
   }
   float alpha = 0.f, beta = 0.f;
@@ -380,18 +410,18 @@ __global__ __launch_bounds__(256) void k_cgs(PcgArgs g, int k, int R, int nbands
   // row o inside the band (stores and dot products only there); so8: the
   // store offset of row o, out of range (the store is dropped) outside the
   // band, so that every row step issues the same memory operations
-  auto inband = [&](int o) { return o >= r0 && o < r1; };
+  auto inband = [&](int o) { return (unsigned)(o - r0) < nrb; };
   // (the empty asm keeps the select: without it the compiler threads the
   // stores back into the two arms of the inband branch below them)
-  auto so8 = [&](int o) {
-    unsigned ro = inband(o) ? orow(o) * rowb8 : CG_ROW_OOB;
+  auto so8 = [&](int o, unsigned c8) {  // c8 = rw8(o)
+    unsigned ro = inband(o) ? c8 : CG_ROW_OOB;
     asm("" : "+s"(ro));
     return soff8 + ro;
   };
   if (live) {
     if (role == 0) {
-      QA[0] = put_rec(ns - 2, SGp[0]);  // ring slots of rows ns - 2, ns - 1 at u = 0
-      QA[1] = put_rec(ns - 1, SGp[1]);
+      QA[0] = put_rec(rslot(ns - 2), SGp[0]);  // ring slots of rows ns - 2, ns - 1 at u = 0
+      QA[1] = put_rec(rslot(ns - 1), SGp[1]);
     }
     __syncthreads();
     CGS_T0
@@ -404,19 +434,57 @@ __global__ __launch_bounds__(256) void k_cgs(PcgArgs g, int k, int R, int nbands
     // timed lanes run a fine solve one block per CU beside other lanes' work)
     else __builtin_amdgcn_s_setprio(1);
     // each wave runs its own role's loop (registers of one role only), one
-    // block barrier per row step in every role (same step count)
+    // block barrier per row step in every role (same step count).  A trip is
+    // eight row steps, each an instance of one generic lambda: u is a
+    // compile-time constant where the register rings are indexed, so the
+    // rings are split into registers before any loop pass sees them (as an
+    // unrolled loop over u they were kept as 32-register tuples, which the
+    // register allocator copied whole: up to 80 moves in a row step).  Whole
+    // trips run without a test between their steps; only the last, partial
+    // trip tests n against ne.  With the test inside every step the compiler
+    // merged the early exits into a flag tested at the top of the next step,
+    // i.e. a path that reaches a step without the memory operations of the
+    // step before, and sized every vmcnt wait for that path (load distance 1
+    // instead of CGS_PF / CGS_PF2; see the note above CGS_PF2)
 #define CGS_STEPS(...)                                                    \
-  for (int n0 = ns; n0 <= ne; n0 += 8) {                                  \
-    _Pragma("unroll") for (int u = 0; u < 8; ++u) {                       \
+  {                                                                       \
+    auto cgs_step = [&](int n0, auto cgs_u) __attribute__((always_inline)) { \
+      constexpr int u = decltype(cgs_u)::value;                           \
       const int n = n0 + u;                                               \
-      if (n > ne) break;                                                  \
       __VA_ARGS__                                                         \
       CGS_BAR_BEGIN                                                       \
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");              \
       __builtin_amdgcn_s_barrier();                                       \
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");              \
       CGS_BAR_END                                                         \
+    };                                                                    \
+    int n0 = ns;                                                          \
+    for (; n0 + 7 <= ne; n0 += 8) {                                       \
+      cgs_step(n0, CgsStep<0>{});                                         \
+      cgs_step(n0, CgsStep<1>{});                                         \
+      cgs_step(n0, CgsStep<2>{});                                         \
+      cgs_step(n0, CgsStep<3>{});                                         \
+      cgs_step(n0, CgsStep<4>{});                                         \
+      cgs_step(n0, CgsStep<5>{});                                         \
+      cgs_step(n0, CgsStep<6>{});                                         \
+      cgs_step(n0, CgsStep<7>{});                                         \
     }                                                                     \
+    do {                                                                  \
+      if (n0 > ne) break;                                                 \
+      cgs_step(n0, CgsStep<0>{});                                         \
+      if (n0 + 1 > ne) break;                                             \
+      cgs_step(n0, CgsStep<1>{});                                         \
+      if (n0 + 2 > ne) break;                                             \
+      cgs_step(n0, CgsStep<2>{});                                         \
+      if (n0 + 3 > ne) break;                                             \
+      cgs_step(n0, CgsStep<3>{});                                         \
+      if (n0 + 4 > ne) break;                                             \
+      cgs_step(n0, CgsStep<4>{});                                         \
+      if (n0 + 5 > ne) break;                                             \
+      cgs_step(n0, CgsStep<5>{});                                         \
+      if (n0 + 6 > ne) break;                                             \
+      cgs_step(n0, CgsStep<6>{});                                         \
+    } while (0);                                                          \
   }
 // register-ring index of row n + d: (u + d) mod ring size
 #define R8(d) ((u + (d) + 16) & 7)
@@ -426,31 +494,39 @@ __global__ __launch_bounds__(256) void k_cgs(PcgArgs g, int k, int R, int nbands
 #define RRI(d) ((u + (d) + 16) & (CGS_RIN - 1))
 #define RW2(d) ((u + (d) + 16) & (CGS_W2N - 1))
     if (role == 0) {
+      // running offsets of rows n + PF (c4, c8), n + PF - 1 (c8p), n - 1 (cs)
+      unsigned c4 = rw4(ns + CGS_PF), c8 = rw8(ns + CGS_PF), c8p = rw8(ns + CGS_PF - 1), cs = rw8(ns - 1);
+      int rs = rslot(ns);
       CGS_STEPS({
-        load_raw(n + CGS_PF, SG[RSG(CGS_PF)]);
-        PO[R8(CGS_PF)] = load_po(n + CGS_PF);
-        RI[RRI(CGS_PF - 1)] = load_rin(n + CGS_PF - 1);
+        load_raw(n + CGS_PF, c4, SG[RSG(CGS_PF)]);
+        PO[R8(CGS_PF)] = load_po(c8);
+        RI[RRI(CGS_PF - 1)] = load_rin(c8p);
         // A) row n-1: r = r_in - alpha A p_old, y = D^-1 r
 #if CGS_W0REG
         const cg_f2 wu[2] = {QA[R2(-2)].wy[0], QA[R2(-2)].wy[1]};  // before row n takes the slot
         const CgRec q1 = QA[R2(-1)];
-        QA[R2(0)] = put_rec(n, SG[RSG(0)]);
+        QA[R2(0)] = put_rec(rs, SG[RSG(0)]);
 #else
-        put_rec(n, SG[RSG(0)]);
-        const CgRec q1 = get_rec(n - 1);
+        put_rec(rs, SG[RSG(0)]);
+        const CgRec q1 = get_rec(rsl(rs, 1));
         cg_f2 wu[2];
-        get_wy(n - 2, wu);
+        get_wy(rsl(rs, 2), wu);
 #endif
         cg_f4 r = RI[RRI(-1)];
         if (!FIRST) r -= alpha * (cgr_diag_raw(SG[RSG(-1)], PO[R8(-1)]) - cgr_nsum(PO[R8(-2)], PO[R8(-1)], PO[R8(0)], q1, wu));
         const cg_f4 y = cgr_minv(q1, r);
         s_y[(n - 1) & 7][lane] = make_float4(y.x, y.y, y.z, y.w);
         const int o = n - 1;
-        cg_st4(rro, so8(o), r);
+        cg_st4(rro, so8(o, cs), r);
         if (inband(o)) {
           acc[4] += (double)mdot(r, r);
           acc[3] += (double)(c0 * mdot(r, y));
         }
+        c4 += step4;
+        c8p = c8;
+        c8 += step8;
+        cs += step8;
+        CGS_RS_NEXT(rs);
       })
     } else if (role == 1) {
       // Horner, degree 5: g4 = c4 y + c5 B y (row n-3), g3 = c3 y + B g4
@@ -461,10 +537,10 @@ __global__ __launch_bounds__(256) void k_cgs(PcgArgs g, int k, int R, int nbands
         const float4 a = s_y[t & 7][lane];
         return cg_f4{a.x, a.y, a.z, a.w};
       };
-#define CGS_REC1(d) get_rec(n + (d))
+#define CGS_REC1(d) get_rec(rslot(n + (d)))
 #define CGS_WY1(d, w) \
   cg_f2 w[2];         \
-  get_wy(n + (d), w)
+  get_wy(rslot(n + (d)), w)
 #define CGS_Y1(d) yrow(n + (d))
       CGS_STEPS({
         CGS_WY1(-7, w7);
@@ -498,14 +574,17 @@ __global__ __launch_bounds__(256) void k_cgs(PcgArgs g, int k, int R, int nbands
 #undef CGS_Y1
     } else if (role == 2) {
       cg_f4 PP[4] = {zero4, zero4, zero4, zero4}, ZZ[2] = {zero4, zero4};
+      // running offsets of rows n + PF2 - 8 (c8) and n - 8 (cs)
+      unsigned c8 = rw8(ns + CGS_PF2 - 8), cs = rw8(ns - 8);
+      int rs = rslot(ns);
       CGS_STEPS({
-        PO2[RW2(CGS_PF2 - 8)] = load_po(n + CGS_PF2 - 8);
-        XI[RW2(CGS_PF2 - 8)] = load_x(n + CGS_PF2 - 8);
+        PO2[RW2(CGS_PF2 - 8)] = load_po(c8);
+        XI[RW2(CGS_PF2 - 8)] = load_x(n + CGS_PF2 - 8, c8);
         // D) row n-8: z = c0 y + D^-1 N g1, p = z + beta p_old, x += alpha p_old
         {
-          const CgRec q4 = get_rec(n - 8);
+          const CgRec q4 = get_rec(rsl(rs, 8));
           cg_f2 wu[2];
-          get_wy(n - 9, wu);
+          get_wy(rsl(rs, 9), wu);
           const cg_f4 ng = cgr_nsum(ld4(s_g1, n - 9), ld4(s_g1, n - 8), ld4(s_g1, n - 7), q4, wu);
           const float4 b = s_y[(n - 8) & 7][lane];
           const cg_f4 yr = {b.x, b.y, b.z, b.w};
@@ -517,16 +596,16 @@ __global__ __launch_bounds__(256) void k_cgs(PcgArgs g, int k, int R, int nbands
           if (!(rv && ok1)) { p.z = 0.f; p.w = 0.f; }
           PP[R4(-8)] = p;
           ZZ[R2(-8)] = z;
-          const unsigned so = so8(o);
+          const unsigned so = so8(o, cs);
           cg_st4(rpn, so, p);
           cg_st4(rx, so, FIRST ? zero4 : XI[RW2(-8)] + alpha * PO2[RW2(-8)]);
           if (inband(o)) acc[3] += (double)mdot(yr, ng);
         }
         // E) row n-9: q = A p, y_q = D^-1 q
         {
-          const CgRec q5 = get_rec(n - 9);
+          const CgRec q5 = get_rec(rsl(rs, 9));
           cg_f2 wu[2];
-          get_wy(n - 10, wu);
+          get_wy(rsl(rs, 10), wu);
           const cg_f4 pm = PP[R4(-9)];
           const cg_f4 q = cgr_diag(q5, pm) -
                           cgr_nsum(PP[R4(-10)], pm, PP[R4(-8)], q5, wu);
@@ -539,6 +618,9 @@ __global__ __launch_bounds__(256) void k_cgs(PcgArgs g, int k, int R, int nbands
             acc[2] += (double)(c0 * mdot(q, yq));
           }
         }
+        c8 += step8;
+        cs += step8;
+        CGS_RS_NEXT(rs);
       })
     } else {
       // q.M^-1 q = sum_i c_i T_i with v0 = y_q, v1 = B v0, v2 = B v1:
@@ -546,13 +628,16 @@ __global__ __launch_bounds__(256) void k_cgs(PcgArgs g, int k, int R, int nbands
       // T5 = v2.N v2 (row n-12; T5 counts each edge once, by its right /
       // lower pixel)
       cg_f4 V1[4] = {zero4, zero4, zero4, zero4}, V2[2] = {zero4, zero4};
+      int rs = rslot(ns);
+      const int ve0 = flip ? r0 : r0 + 1;
+      const unsigned nve = flip ? nrb + 1u : nrb - 1u;
       CGS_STEPS({
         // row n's record: raw since wave 0 stored it at step n - 1; stage A
         // reads it at step n + 1
         {
-          const CgRec q6 = get_rec(n - 11);
+          const CgRec q6 = get_rec(rsl(rs, 11));
           cg_f2 wu[2];
-          get_wy(n - 12, wu);
+          get_wy(rsl(rs, 12), wu);
           const cg_f4 yq = ld4(s_yq, n - 11);
           const cg_f4 ny = cgr_nsum(ld4(s_yq, n - 12), yq, ld4(s_yq, n - 10), q6, wu);
           const cg_f4 v1 = cgr_minv(q6, ny);
@@ -564,9 +649,9 @@ __global__ __launch_bounds__(256) void k_cgs(PcgArgs g, int k, int R, int nbands
           }
         }
         {
-          const CgRec q7 = get_rec(n - 12);
+          const CgRec q7 = get_rec(rsl(rs, 12));
           cg_f2 wy7[2];
-          get_wy(n - 13, wy7);
+          get_wy(rsl(rs, 13), wy7);
           const cg_f4 v1 = V1[R4(-12)];
           const cg_f4 nv = cgr_nsum(V1[R4(-13)], v1, V1[R4(-11)], q7, wy7);
           const cg_f4 v2 = cgr_minv(q7, nv);
@@ -578,7 +663,9 @@ __global__ __launch_bounds__(256) void k_cgs(PcgArgs g, int k, int R, int nbands
           // its virtual rows r0 .. r1 (the band below it in the walk is even
           // and cannot take the edge: it has no v2 past its own last row);
           // an even band then takes its inner edges only
-          const bool vedge = flip ? o >= r0 && o <= r1 : o > r0 && o < r1;
+          // (flipped: o in [r0, r1]; else o in (r0, r1): one range test, its
+          // bounds set before the walk)
+          const bool vedge = (unsigned)(o - ve0) < nve;
           if (inband(o)) {
             const cg_f2 w0 = cg_lo(v2), w1 = cg_hi(v2);
             const cg_f2 h0 = cg_left2(q7.wx[1]) * cg_left2(w1);
@@ -591,6 +678,7 @@ __global__ __launch_bounds__(256) void k_cgs(PcgArgs g, int k, int R, int nbands
             acc[2] += (double)((dm0 ? t.x + t.y : 0.f) + (dm1 ? t.z + t.w : 0.f));
           }
         }
+        CGS_RS_NEXT(rs);
       })
     }
 #undef R8
@@ -600,6 +688,7 @@ __global__ __launch_bounds__(256) void k_cgs(PcgArgs g, int k, int R, int nbands
 #undef RRI
 #undef RW2
 #undef CGS_STEPS
+#undef CGS_RS_NEXT
     CGS_T1
   }
   write_partials<5>(acc, g.part_wr, lds);
