@@ -120,7 +120,15 @@ __device__ __forceinline__ cg_f4 cgr_diag_raw(const CgRaw &c, cg_f4 f) {
 //   wave 3: F) v1 and T1, T2 (row n-11), v2 and T3..T5 (row n-12)
 // with one block barrier per row step; rows cross waves through small LDS
 // rings (y, g1, y_q; records in a 14-row ring), a wave's own rows stay in
-// registers.  (The round-1 form of this iteration, since removed, gave each
+// registers, and so does what a wave has read and needs again at a later
+// step: wave 0 its records of rows n-1, n-2 (CGS_W0REG), wave 2 the records
+// of rows n-8, n-9 with the vertical weights of row n-10 and the g1 rows
+// n-7 .. n-9, wave 3 the records of rows n-11, n-12 with the vertical
+// weights of row n-13 and the y_q rows n-10 .. n-12.  Per row step wave 2
+// reads one record, one g1 row and one y row from LDS and wave 3 one record
+// and one y_q row; the vertical weights of the row above a stage's own come
+// out of that row's record, never from a read of their own, except wave 1's
+// of row n-7, which has no record beside it.  (The round-1 form of this iteration, since removed, gave each
 // wave its own band and the whole pipeline: its record ring allowed one wave
 // per SIMD and 1.6x the rows read.)  Here 74 KB of LDS per block allow 2 blocks per CU (R = 39 at
 // 1080p) and a step costs only the heaviest wave's share.  Stage lags follow
@@ -128,8 +136,9 @@ __device__ __forceinline__ cg_f4 cgr_diag_raw(const CgRaw &c, cg_f4 f) {
 // earlier steps; the band is walked for n in [r0 - 8, r1 + 11] (an odd band,
 // walked bottom to top, to r1 + 12: stage F's T5 seam edge) so that every
 // row a required stage reads was produced.
-// Rejected variants of this kernel (record split over waves 0 / 3, register
-// record rings, raw-D stage E, pair-block splitting, trimmed drain loads)
+// Rejected variants of this kernel (record split over waves 0 / 3, the
+// round-4 register record rings, raw-D stage E, pair-block splitting, trimmed
+// drain loads)
 // are recorded with their measurements in DESIGN.md §3; the commits that
 // measured them hold their source.
 #define CGS_NREC 14
@@ -357,6 +366,13 @@ __global__ __launch_bounds__(256) void k_cgs(PcgArgs g, int k, int R, int nbands
     return cg_mask1<ODD>(cg_ld4(rx, off8 + (!xz && (unsigned)(t - r0) < nrb ? c8 : CG_ROW_OOB)), ok1);
   };
   const bool dm0 = out_lane && ok0, dm1 = out_lane && ok1;
+  // (jc is even, so in the even-width instances dm0 == dm1 and one select per
+  // masked sum, dm0 ? a + b : 0, gives the same bits, as does one condition
+  // for stage D's mask on p.  Measured and left out: the compiler then
+  // branches around the sums; per steady step of <false, false> wave 2 grows
+  // 171 -> 178 instructions (v_mov_b32 23 -> 35) and wave 3 121 -> 129, and
+  // the timed bench loses 0.5 %: 56.28 +- 0.06 vs 56.59 +- 0.07 pairs/s, 5
+  // alternating runs each on one box (profiles/cgs_record_reads/))
   auto mdot = [&](cg_f4 a, cg_f4 b) {
     const cg_f2 p = cg_lo(a) * cg_lo(b), q = cg_hi(a) * cg_hi(b);
     return (dm0 ? p.x + p.y : 0.f) + (dm1 ? q.x + q.y : 0.f);
@@ -544,29 +560,26 @@ __global__ __launch_bounds__(256) void k_cgs(PcgArgs g, int k, int R, int nbands
 #define CGS_Y1(d) yrow(n + (d))
       CGS_STEPS({
         CGS_WY1(-7, w7);
+        // the four records first: the wu of a stage is the wy of the next
+        // stage's record (the compiler had merged those reads already: 23 LDS
+        // instructions per step before and after, 133 -> 128 instructions)
+        const CgRec q3 = CGS_REC1(-3), q4 = CGS_REC1(-4), q5 = CGS_REC1(-5), q6 = CGS_REC1(-6);
         {
-          const CgRec q = CGS_REC1(-3);
-          CGS_WY1(-4, wu);
           const cg_f4 y0 = CGS_Y1(-3);
-          const cg_f4 ny = cgr_nsum(CGS_Y1(-4), y0, CGS_Y1(-2), q, wu);
-          G4[R4(-3)] = c4 * y0 + c5 * cgr_minv(q, ny);
+          const cg_f4 ny = cgr_nsum(CGS_Y1(-4), y0, CGS_Y1(-2), q3, q4.wy);
+          G4[R4(-3)] = c4 * y0 + c5 * cgr_minv(q3, ny);
         }
         {
-          const CgRec q = CGS_REC1(-4);
-          CGS_WY1(-5, wu);
-          const cg_f4 ng = cgr_nsum(G4[R4(-5)], G4[R4(-4)], G4[R4(-3)], q, wu);
-          G3[R4(-4)] = c3 * CGS_Y1(-4) + cgr_minv(q, ng);
+          const cg_f4 ng = cgr_nsum(G4[R4(-5)], G4[R4(-4)], G4[R4(-3)], q4, q5.wy);
+          G3[R4(-4)] = c3 * CGS_Y1(-4) + cgr_minv(q4, ng);
         }
         {
-          const CgRec q = CGS_REC1(-5);
-          CGS_WY1(-6, wu);
-          const cg_f4 ng = cgr_nsum(G3[R4(-6)], G3[R4(-5)], G3[R4(-4)], q, wu);
-          G2[R4(-5)] = c2 * CGS_Y1(-5) + cgr_minv(q, ng);
+          const cg_f4 ng = cgr_nsum(G3[R4(-6)], G3[R4(-5)], G3[R4(-4)], q5, q6.wy);
+          G2[R4(-5)] = c2 * CGS_Y1(-5) + cgr_minv(q5, ng);
         }
         {
-          const CgRec q = CGS_REC1(-6);
-          const cg_f4 ng = cgr_nsum(G2[R4(-7)], G2[R4(-6)], G2[R4(-5)], q, w7);
-          st4(s_g1, n - 6, c1 * CGS_Y1(-6) + cgr_minv(q, ng));
+          const cg_f4 ng = cgr_nsum(G2[R4(-7)], G2[R4(-6)], G2[R4(-5)], q6, w7);
+          st4(s_g1, n - 6, c1 * CGS_Y1(-6) + cgr_minv(q6, ng));
         }
       })
 #undef CGS_REC1
@@ -574,6 +587,35 @@ __global__ __launch_bounds__(256) void k_cgs(PcgArgs g, int k, int R, int nbands
 #undef CGS_Y1
     } else if (role == 2) {
       cg_f4 PP[4] = {zero4, zero4, zero4, zero4}, ZZ[2] = {zero4, zero4};
+      // What the wave read and needs again: RD the records of rows n-8 (read
+      // at this step for stage D) and n-9 (read one step ago, now stage E's;
+      // its wy is stage D's wu), by R2; the slot row n-8 takes held row n-10,
+      // whose wy is stage E's wu.  G1 the g1 rows n-9 .. n-7 by R4, row n-7
+      // read at this step.  Before: 2 records, 2 wy pairs and 3 g1 rows per
+      // step (14 LDS instructions per steady step of <false, false>, now 7;
+      // 191 -> 171 instructions, the same 23 v_mov_b32).
+      // At loop entry they are initialised to 0, which is what reading them
+      // after the first __syncthreads() would return: the record of a row
+      // r < ns - 2 shares its ring slot with row r + 14, which wave 0 stores
+      // at step r + 14, after the last read of row r at step r + 10 (wave
+      // 3: r + 13), so every read of rows ns-10 .. ns-9 (wave 3: ns-13 ..
+      // ns-12) sees the zeroed slot; a g1 (y_q) row r is stored at step r +
+      // 6 (r + 9), which for rows ns-9, ns-8 (ns-12, ns-11) is before the
+      // walk, i.e. never, and its slot is next stored at step r + 10 (r +
+      // 13), after its last read at step r + 9 (r + 12).
+      // Timed bench, 5 alternating runs each on one box, the same flow
+      // bitwise (profiles/cgs_record_reads/): parent 54.91 +- 0.09, the wy
+      // of a record read in the same step taken from it 55.19 +- 0.07, +
+      // wave 2's carried rows 56.04 +- 0.06, + wave 3's 56.59 +- 0.07
+      // pairs/s; wave 2 72.3 K -> 58.0 K working cycles per launch.  (The
+      // round-4 rings of DESIGN.md §3 were 7 % slower as timed; then wave 0
+      // set the step and the rings were copied whole.)
+      // Also measured and left out: each wave's one new record read issued
+      // at the end of the step before (its row is two barriers old), to be in
+      // flight across the barrier: 57.04 +- 0.19 vs 57.06 +- 0.05 pairs/s,
+      // the fence before the barrier waits for the read anyway.
+      CgRec RD[2] = {};
+      cg_f4 G1[4] = {zero4, zero4, zero4, zero4};
       // running offsets of rows n + PF2 - 8 (c8) and n - 8 (cs)
       unsigned c8 = rw8(ns + CGS_PF2 - 8), cs = rw8(ns - 8);
       int rs = rslot(ns);
@@ -581,11 +623,12 @@ __global__ __launch_bounds__(256) void k_cgs(PcgArgs g, int k, int R, int nbands
         PO2[RW2(CGS_PF2 - 8)] = load_po(c8);
         XI[RW2(CGS_PF2 - 8)] = load_x(n + CGS_PF2 - 8, c8);
         // D) row n-8: z = c0 y + D^-1 N g1, p = z + beta p_old, x += alpha p_old
+        const cg_f2 wuE[2] = {RD[R2(-10)].wy[0], RD[R2(-10)].wy[1]};  // before row n-8 takes the slot
+        RD[R2(-8)] = get_rec(rsl(rs, 8));
+        G1[R4(-7)] = ld4(s_g1, n - 7);
         {
-          const CgRec q4 = get_rec(rsl(rs, 8));
-          cg_f2 wu[2];
-          get_wy(rsl(rs, 9), wu);
-          const cg_f4 ng = cgr_nsum(ld4(s_g1, n - 9), ld4(s_g1, n - 8), ld4(s_g1, n - 7), q4, wu);
+          const CgRec q4 = RD[R2(-8)];
+          const cg_f4 ng = cgr_nsum(G1[R4(-9)], G1[R4(-8)], G1[R4(-7)], q4, RD[R2(-9)].wy);
           const float4 b = s_y[(n - 8) & 7][lane];
           const cg_f4 yr = {b.x, b.y, b.z, b.w};
           const cg_f4 z = c0 * yr + cgr_minv(q4, ng);
@@ -603,12 +646,10 @@ __global__ __launch_bounds__(256) void k_cgs(PcgArgs g, int k, int R, int nbands
         }
         // E) row n-9: q = A p, y_q = D^-1 q
         {
-          const CgRec q5 = get_rec(rsl(rs, 9));
-          cg_f2 wu[2];
-          get_wy(rsl(rs, 10), wu);
+          const CgRec q5 = RD[R2(-9)];
           const cg_f4 pm = PP[R4(-9)];
           const cg_f4 q = cgr_diag(q5, pm) -
-                          cgr_nsum(PP[R4(-10)], pm, PP[R4(-8)], q5, wu);
+                          cgr_nsum(PP[R4(-10)], pm, PP[R4(-8)], q5, wuE);
           const cg_f4 yq = cgr_minv(q5, q);
           st4(s_yq, n - 9, yq);
           const int o = n - 9;
@@ -628,18 +669,26 @@ __global__ __launch_bounds__(256) void k_cgs(PcgArgs g, int k, int R, int nbands
       // T5 = v2.N v2 (row n-12; T5 counts each edge once, by its right /
       // lower pixel)
       cg_f4 V1[4] = {zero4, zero4, zero4, zero4}, V2[2] = {zero4, zero4};
+      // carried as in wave 2 (see there for the values at loop entry): RF the
+      // records of rows n-11 (read at this step) and n-12, whose wy is the wu
+      // of row n-11; the slot row n-11 takes held row n-13, whose wy is wy7.
+      // YQ the y_q rows n-12 .. n-10, row n-10 read at this step.  12 -> 5
+      // LDS instructions per steady step, 144 -> 121 instructions
+      CgRec RF[2] = {};
+      cg_f4 YQ[4] = {zero4, zero4, zero4, zero4};
       int rs = rslot(ns);
       const int ve0 = flip ? r0 : r0 + 1;
       const unsigned nve = flip ? nrb + 1u : nrb - 1u;
       CGS_STEPS({
         // row n's record: raw since wave 0 stored it at step n - 1; stage A
         // reads it at step n + 1
+        const cg_f2 wy7[2] = {RF[R2(-13)].wy[0], RF[R2(-13)].wy[1]};  // before row n-11 takes the slot
+        RF[R2(-11)] = get_rec(rsl(rs, 11));
+        YQ[R4(-10)] = ld4(s_yq, n - 10);
         {
-          const CgRec q6 = get_rec(rsl(rs, 11));
-          cg_f2 wu[2];
-          get_wy(rsl(rs, 12), wu);
-          const cg_f4 yq = ld4(s_yq, n - 11);
-          const cg_f4 ny = cgr_nsum(ld4(s_yq, n - 12), yq, ld4(s_yq, n - 10), q6, wu);
+          const CgRec q6 = RF[R2(-11)];
+          const cg_f4 yq = YQ[R4(-11)];
+          const cg_f4 ny = cgr_nsum(YQ[R4(-12)], yq, YQ[R4(-10)], q6, RF[R2(-12)].wy);
           const cg_f4 v1 = cgr_minv(q6, ny);
           V1[R4(-11)] = v1;
           const int o = n - 11;
@@ -649,9 +698,7 @@ __global__ __launch_bounds__(256) void k_cgs(PcgArgs g, int k, int R, int nbands
           }
         }
         {
-          const CgRec q7 = get_rec(rsl(rs, 12));
-          cg_f2 wy7[2];
-          get_wy(rsl(rs, 13), wy7);
+          const CgRec q7 = RF[R2(-12)];
           const cg_f4 v1 = V1[R4(-12)];
           const cg_f4 nv = cgr_nsum(V1[R4(-13)], v1, V1[R4(-11)], q7, wy7);
           const cg_f4 v2 = cgr_minv(q7, nv);
