@@ -126,9 +126,10 @@ __device__ __forceinline__ cg_f4 cgr_diag_raw(const CgRaw &c, cg_f4 f) {
 // n-7 .. n-9, wave 3 the records of rows n-11, n-12 with the vertical
 // weights of row n-13 and the y_q rows n-10 .. n-12.  Per row step wave 2
 // reads one record, one g1 row and one y row from LDS and wave 3 one record
-// and one y_q row; the vertical weights of the row above a stage's own come
-// out of that row's record, never from a read of their own, except wave 1's
-// of row n-7, which has no record beside it.  (The round-1 form of this iteration, since removed, gave each
+// and one y_q row; wave 1 keeps the records of rows n-3 .. n-6 with the
+// vertical weights of row n-7 and reads one record and its five y rows.  The
+// vertical weights of the row above a stage's own come out of that row's
+// record, never from a read of their own.  (The round-1 form of this iteration, since removed, gave each
 // wave its own band and the whole pipeline: its record ring allowed one wave
 // per SIMD and 1.6x the rows read.)  Here 74 KB of LDS per block allow 2 blocks per CU (R = 39 at
 // 1080p) and a step costs only the heaviest wave's share.  Stage lags follow
@@ -300,7 +301,7 @@ __global__ __launch_bounds__(256) void k_cgs(PcgArgs g, int k, int R, int nbands
     return s < 0 ? s + CGS_NREC : s;
   };
 #define CGS_RS_NEXT(rs) rs = (rs) + 1 == CGS_NREC ? 0 : (rs) + 1
-  // put_rec / get_rec / get_wy take the slot
+  // put_rec / get_rec / get_wy take the slot (get_wy: wave 0 without CGS_W0REG)
   auto put_rec = [&](int slot, const CgRaw &c) {
     CgCoef cc;
     cc.a = c.a;
@@ -337,12 +338,14 @@ __global__ __launch_bounds__(256) void k_cgs(PcgArgs g, int k, int R, int nbands
     r.mb[1] = cg_f2{d.z, d.w};
     return r;
   };
+#if !CGS_W0REG
   auto get_wy = [&](int slot, cg_f2 (&wu)[2]) {  // vertical weight pairs only
     const float2 *q = reinterpret_cast<const float2 *>(&ring[slot][0][lane]);
     const float2 a = q[1], b = q[129];
     wu[0] = cg_f2{a.x, a.y};
     wu[1] = cg_f2{b.x, b.y};
   };
+#endif
   auto ld4 = [&](float4 (&rg)[4][64], int t) {
     const float4 v = rg[t & 3][lane];
     return cg_f4{v.x, v.y, v.z, v.w};
@@ -553,17 +556,40 @@ __global__ __launch_bounds__(256) void k_cgs(PcgArgs g, int k, int R, int nbands
         const float4 a = s_y[t & 7][lane];
         return cg_f4{a.x, a.y, a.z, a.w};
       };
-#define CGS_REC1(d) get_rec(rslot(n + (d)))
-#define CGS_WY1(d, w) \
-  cg_f2 w[2];         \
-  get_wy(rslot(n + (d)), w)
+      // Carried as in waves 2 and 3: RB the records of rows n-3 (read at this
+      // step for g4) .. n-6, by R4; the slot row n-3 takes held row n-7, whose
+      // wy is g1's wu (w7) and is taken out first.  Before: 4 records and the
+      // wy pair of row n-7 per step (23 LDS instructions per steady step of
+      // <false, false>, now 10: one record, five y rows, the g1 write; 128 ->
+      // 114 instructions, the same 24 v_mov_b32, 246 -> 226 VGPRs).
+      // RB is initialised to 0 at loop entry, which is what reading those
+      // records after the first __syncthreads() would return.  Wave 0 stores
+      // the record of row r at step r (rows ns-2, ns-1 before the walk), a
+      // barrier ahead of this wave's first read of it at step r + 3; the
+      // reads this replaces are at steps r + 4 .. r + 7 (r + 7: the wy alone),
+      // and the slot is next stored with row r + 14 at step r + 14, so what
+      // was read at step r + 3 is what they return.  Rows ns-4 .. ns-7, which
+      // RB stands for at step ns, are below ns - 2 and never stored; their
+      // zeroed slots are first stored at steps ns + 10 .. ns + 7, after the
+      // last reads of those rows at steps ns + 3 .. ns.
+      // Timed bench, 5 alternating runs each on one box, the same iterates and
+      // flow bitwise (profiles/cgs_wave1_reads/): parent 56.20 +- 0.13, RB
+      // 57.01 +- 0.12 pairs/s (second box 56.19 +- 0.07, 56.93 +- 0.04).
+      // Also measured and left out, neither clearing 3 sd on either box:
+      // + the y rows n-3 .. n-6 carried in a ring YR[8] by R8, one s_y read
+      //   per step (6 LDS instructions, 106 instructions, 240 VGPRs): 57.01
+      //   +- 0.12 (second box 57.10 +- 0.06, +0.3 %, 2.8 sd);
+      // + the slot from the running counter as in the other roles instead of
+      //   rslot(): on RB alone 57.06 +- 0.10 (second box only), on RB + YR
+      //   57.22 +- 0.32 (57.03 +- 0.12).  The steady step has the same
+      //   instruction counts with it: the compiler already steps the slot.
+      CgRec RB[4] = {};
 #define CGS_Y1(d) yrow(n + (d))
       CGS_STEPS({
-        CGS_WY1(-7, w7);
-        // the four records first: the wu of a stage is the wy of the next
-        // stage's record (the compiler had merged those reads already: 23 LDS
-        // instructions per step before and after, 133 -> 128 instructions)
-        const CgRec q3 = CGS_REC1(-3), q4 = CGS_REC1(-4), q5 = CGS_REC1(-5), q6 = CGS_REC1(-6);
+        const cg_f2 w7[2] = {RB[R4(-7)].wy[0], RB[R4(-7)].wy[1]};  // before row n-3 takes the slot
+        RB[R4(-3)] = get_rec(rslot(n - 3));
+        // the wu of a stage is the wy of the next stage's record
+        const CgRec q3 = RB[R4(-3)], q4 = RB[R4(-4)], q5 = RB[R4(-5)], q6 = RB[R4(-6)];
         {
           const cg_f4 y0 = CGS_Y1(-3);
           const cg_f4 ny = cgr_nsum(CGS_Y1(-4), y0, CGS_Y1(-2), q3, q4.wy);
@@ -582,8 +608,6 @@ __global__ __launch_bounds__(256) void k_cgs(PcgArgs g, int k, int R, int nbands
           st4(s_g1, n - 6, c1 * CGS_Y1(-6) + cgr_minv(q6, ng));
         }
       })
-#undef CGS_REC1
-#undef CGS_WY1
 #undef CGS_Y1
     } else if (role == 2) {
       cg_f4 PP[4] = {zero4, zero4, zero4, zero4}, ZZ[2] = {zero4, zero4};

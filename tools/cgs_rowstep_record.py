@@ -1,6 +1,7 @@
 """Record the fixtures of tests/test_gpu_cgs_rowstep.py, or with --set
-record_reads those of tests/test_gpu_cgs_record_reads.py, from the library
-in the tree (to be run on the commit whose iterates are the reference):
+record_reads / wave1_reads those of tests/test_gpu_cgs_record_reads.py /
+tests/test_gpu_cgs_wave1_reads.py, from the library in the tree (to be run
+on the commit whose iterates are the reference):
 
     python tools/cgs_rowstep_record.py [--set rowstep] [--out tests/golden]
 
@@ -22,7 +23,7 @@ sys.path[:0] = [os.path.join(ROOT, "optical-flow-python_amd"), os.path.join(ROOT
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--set", default="rowstep", choices=["rowstep", "record_reads"])
+    ap.add_argument("--set", default="rowstep", choices=["rowstep", "record_reads", "wave1_reads"])
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     RC = importlib.import_module(f"cgs_{args.set}_cases")
