@@ -1432,6 +1432,130 @@ int of_masks_push(of_ctx *ctx, const float *frame, const uint8_t *mask, uint8_t 
 int of_masks_close(of_ctx *ctx);
 
 /*
+ * Blind temporal consistency: the flicker of a per-frame operator removed
+ * (Bonneel et al. 2015; Lai et al. 2018 without the network).  Beside the clip
+ * V there is a second clip P, the same frames after an operator that knows
+ * nothing about time (tone mapping, grading, dehazing, colourisation, ...):
+ * every frame of P looks right, the clip flickers.  Output frame t keeps the
+ * gradients of P_t and leans, where the original frames say the surface is
+ * the same, on the previous output warped along the backward flow: a screened
+ * Poisson problem per frame.  Everything in double from the fp32 or byte
+ * inputs, no fma contraction, in exactly the order written (a numpy float64
+ * restatement gives the same bits); bil and inside as defined above ("Using a
+ * flow on an image").  H * W >= 2^31: OF_ENOTSUP.  Any option out of range or
+ * not finite: OF_EINVAL, checked on the host before any launch (every entry
+ * checks the whole struct).
+ *
+ * The screened problem, per channel on an H x W frame: a target plane P (fp32,
+ * whose gradients are wanted), an anchor plane A (fp64) and a screening plane
+ * q >= 0 (fp64).  For pixel p, N(p) is its 4-neighbours inside the frame in
+ * the order up, down, left, right, and deg = |N(p)|:
+ *   (deg + q_p) x_p - sum_{n in N(p)} x_n = b_p
+ *   g = 0.0; for n in N(p):  g = g + (P_p - P_n)
+ *   b_p = g + q_p * A_p
+ * The start value is x = P.  With q == 0 everywhere the start's residual is
+ * exactly 0 (the differences and sums of fp32 values of one scale are exact in
+ * double) and the result is P to the bit; that singular case gets no special
+ * handling.  A 1 x 1 frame has deg = 0: x = (q * A) / q if q > 0, else P.
+ *
+ * The solver is the fixed W-cycle schedule of "Gradient-domain blending" above,
+ * with no reduction and no stopping test: a function of (H, W, options) alone.
+ *   Levels and L as there.  Every level's window is its whole grid plus an
+ *   apron of one cell of level L on every side, anchored at the frame's origin.
+ *   d and w are those of the all-unknown problem (level 0: d = deg, w = 1
+ *   towards a neighbour inside the frame; 0 outside the frame), their Galerkin
+ *   coarsening the one stated there.  A double plane q per level is new: level
+ *   0 as given (0.0 outside the frame), level l+1 the Galerkin term of
+ *   piecewise-constant transfer,
+ *     q = ((q(c00) + q(c01)) + q(c10)) + q(c11)
+ *   A cell is solved for where (double)d + q > 0.
+ *   Sweep (red-black, colour k = 0, then 1, as there):
+ *     t = b; for n = up, down, left, right with w_n != 0: t = t + (double)w_n * x_n
+ *     x = t / ((double)d + q)
+ *   Residual of a solved cell (0.0 elsewhere):
+ *     r = b - ((double)d + q) * x; for n as above: r = r + (double)w_n * x_n
+ *   Restriction, the correction x = x + 1.5 * x_parent (on the cells with
+ *   d > 0; 1.5 was measured again for this operator against 1.0 and 1.25,
+ *   DESIGN.md) and the cycle as there.  The solve: x = P, then `cycles` times
+ *   cycle(0).
+ * The options are an of_blend_opts with its ranges; OF_CONSIST_CYCLES (5) is
+ * the cycle count at which every convergence case of the tests (q in patches
+ * of 0, 1e-3, 1 and 1e3) and the tests' scene are within half an 8-bit level
+ * of the exact solution.
+ *
+ * The consistency step of frame t: the frame V_t and its predecessor V_{t-1}
+ * (H x W x C, C 1..4), the processed frame P_t (H x W x Cp, Cp 1..4,
+ * independent of C: a grey clip can be colourised), the previous output
+ * O_{t-1} (H x W x Cp fp32, as emitted), the flow f from t to t-1 and its
+ * forward-backward state s (NULL: all 0).  With (u, v) = f(i, j):
+ *   w   = of_fuse_weights(center V_t, one neighbour V_{t-1}, flow f, state s;
+ *         sigma, strength, patch), a float plane
+ *   vis = u, v finite && inside(i + v, j + u) && s(i,j) == 0       (w's own rule)
+ *   q   = lambda * (double)w where vis, else 0.0
+ *   A_c = bil(O_{t-1,c}, i + v, j + u) where vis, else 0.0
+ *   O_t = (float) of the screened solve of (P_t, A, q), per channel
+ *   out_weight = w       (where the output leans on the past)
+ * lambda is finite and >= 0 (1).  At 0 the step returns P_t to the bit; a
+ * large lambda returns the warped previous output where it is visible.  sigma
+ * is what the original frames may differ by where they show the same surface.
+ *
+ * Known limits.  The first frame's look is the anchor and errors accumulate
+ * along a long clip: lambda trades flicker against drift, and there is no
+ * long-term keyframe.  Where the forward-backward state or the weight rejects
+ * the past the pixel follows the processed frame alone, so newly revealed
+ * regions can still flicker.  Causal: no look-ahead.  No scale, batch or
+ * stream variant.
+ */
+#define OF_CONSIST_CYCLES 5
+#define OF_CONSIST_MAX_CHANNELS 4
+typedef struct of_consist_opts {
+  of_fuse_opts fuse;    /* sigma, strength, patch of the weight; alpha1, alpha2 session only; radius is not read */
+  of_blend_opts solve;  /* the solver's cycles (5), sweeps (2), coarse_sweeps (32) */
+  double lambda;        /* the weight of the past, finite, >= 0 (1) */
+} of_consist_opts;
+/*
+ * of_screened_solve: the solver on its own.
+ *   target : H x W x C interleaved fp32, C 1..4
+ *   anchor : H x W x C doubles
+ *   weight : H x W doubles, the plane q; a negative or non-finite value: OF_EINVAL
+ *   out    : H x W x C doubles
+ */
+int of_screened_solve(of_ctx *ctx, const float *target, const double *anchor, const double *weight, int H, int W,
+                      int C, const of_blend_opts *opts, double *out);
+/*
+ *   frame, prev_frame : H x W x C
+ *   processed         : H x W x Cp
+ *   prev_out          : H x W x Cp
+ *   flow              : 2 x H x W, frame -> prev_frame
+ *   state             : H x W bytes, or NULL
+ *   out               : H x W x Cp
+ *   out_weight        : H x W, or NULL
+ */
+int of_consist_step(of_ctx *ctx, const float *frame, const float *prev_frame, int H, int W, int C,
+                    const float *processed, const float *prev_out, int Cp, const float *flow, const uint8_t *state,
+                    const of_consist_opts *opts, float *out, float *out_weight);
+/*
+ * The temporal consistency session: one per context, beside the other kinds.
+ * It keeps the previous frame V_{k-1} and the previous output O_{k-1} on the
+ * device; their bytes count in OF_OPT_DEVICE_BYTES from open to close, and
+ * of_ctx_destroy closes it.  C is 1 or 3, Cp 1..4.  It is not a delayed
+ * emitter: push k returns output k.  Push 0 returns `processed` to the bit
+ * (out_weight 0 everywhere).  Push k > 0 estimates the pair (k-1, k) in both
+ * directions at full resolution from zero flows with a fresh copy of the
+ * open's params and runs the step along the backward flow with its state:
+ * bitwise
+ *   fw, bw, state_fw, state_bw = of_estimate_flow_bidir(V_{k-1}, V_k; alpha1, alpha2)
+ *   out, out_weight = of_consist_step(V_k, V_{k-1}, processed, O_{k-1}, bw, state_bw)
+ * out: H x W x Cp; out_weight: H x W or NULL.  A second open is refused
+ * (OF_EINVAL), as are push and close without an open session.  It is not a
+ * kind of_session_set_flow_scale takes (there is no OF_SESSION_* bit for it):
+ * its pairs are estimated at full resolution.
+ */
+int of_consist_open(of_ctx *ctx, const of_params *params, int H, int W, int C, int Cp, const of_consist_opts *opts);
+int of_consist_push(of_ctx *ctx, const float *frame, const float *processed, float *out, float *out_weight);
+int of_consist_close(of_ctx *ctx);
+
+/*
  * Layered motion segmentation.  of_fit_motion finds one motion, the dominant
  * one; of_segment_motion splits a flow into up to K parametric motions of one
  * model, a label per pixel and a class for what no motion explains

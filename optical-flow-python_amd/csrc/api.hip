@@ -170,7 +170,7 @@ int of_get_option(of_ctx *c, int option, int64_t *value) {
     case OF_OPT_DEVICE_BYTES: {
       // grow-only device buffers of the context and its lanes: the arena
       // chunks, the pipelined SOR's sweep ring and the RCCL gather buffer;
-      // and the open sessions' (point tracker, temporal denoiser, stabiliser, super-resolver, inpainter, mask propagator) buffers
+      // and the open sessions' (point tracker, temporal denoiser, stabiliser, super-resolver, inpainter, mask propagator, temporal consistency) buffers
       auto held = [](const of_ctx *x) {
         return (int64_t)(x->arena.reserved() + x->sor_ring_cap + x->gather_cap);
       };

@@ -26,6 +26,7 @@
 //   kernels_sr.hip     multi-frame super-resolution: the resampling along the flows, the back-projection step
 //   kernels_inpaint.hip flow-guided video inpainting: mask growing and the pair weight, the fill along the flows
 //   kernels_poisson.hip gradient-domain blending: the multilevel Poisson solver's steps, the blended fill's label planes and result
+//   kernels_screen.hip blind temporal consistency: the screened multilevel solver's steps, its setup along the flow and result
 //   kernels_mask.hip   mask propagation: the carry along the backward flow, the colour-guided vote, the mode filter
 //   kernels_motion.hip global motion: the passes of the robust parametric fit, the affine warp
 //   kernels_layers.hip layered motion segmentation (uses the fit's passes)
@@ -50,6 +51,7 @@
 //   host_sr.hip     multi-frame super-resolution: the resampling and back-projection, the stage entry, the session
 //   host_poisson.hip the multilevel Poisson solver: levels and windows, setup, the W-cycle schedule, the stage entry
 //   host_inpaint.hip flow-guided video inpainting: mask growing, the fill, the blended fill, the stage entries, the session with its weighted pairs
+//   host_screen.hip blind temporal consistency: the screened solve's levels and schedule, the step, the stage entries, the session
 //   host_mask.hip   mask propagation: one step, the stage entry, the session
 //   host_motion.hip global motion: the robust parametric fit, the affine warp, path smoothing, the stabiliser session
 //   host_layers.hip layered motion segmentation: hypotheses, extraction, joint rounds, the stage entry
@@ -87,6 +89,7 @@
 #include "kernels_sr.hip"
 #include "kernels_inpaint.hip"
 #include "kernels_poisson.hip"
+#include "kernels_screen.hip"
 #include "kernels_mask.hip"
 #include "kernels_motion.hip"
 #include "kernels_layers.hip"
@@ -109,6 +112,7 @@
 #include "host_sr.hip"
 #include "host_poisson.hip"
 #include "host_inpaint.hip"
+#include "host_screen.hip"
 #include "host_mask.hip"
 #include "host_motion.hip"
 #include "host_layers.hip"

@@ -168,7 +168,7 @@ struct PairPool {
 // state and the device allocations, which are the session's own and outlive
 // the arena's per-call reset.  A context holds at most one of each kind.
 // of_session_set_flow_scale names the first SES_SCALE_KINDS of them.
-enum { SES_TRACK, SES_DENOISE, SES_STAB, SES_SR, SES_INPAINT, SES_MASKS, SES_KINDS, SES_SCALE_KINDS = SES_SR };
+enum { SES_TRACK, SES_DENOISE, SES_STAB, SES_SR, SES_INPAINT, SES_MASKS, SES_CONSIST, SES_KINDS, SES_SCALE_KINDS = SES_SR };
 struct Session {
   int H = 0, W = 0, C = 0;
   of_params P;        // as given at open; every push starts from a copy
@@ -256,6 +256,14 @@ struct Inpainter : Session {
 struct MaskPropagator : Session {
   of_mask_opts opt;
   uint8_t *mask = nullptr;         // H x W dense, 0 / 1
+};
+
+// the temporal consistency session (of_consist_open, host_screen.hip): a ring
+// of 2 frames and the output of the frame pushed last
+struct Consistency : Session {
+  of_consist_opts opt;
+  int Cp = 0;                      // channels of the processed frames and the outputs
+  float *out = nullptr;            // H x W x Cp dense
 };
 
 // the stabiliser (of_stab_open, host_motion.hip): a ring of R+1 frames; the
@@ -405,7 +413,7 @@ struct of_ctx {
   std::vector<Slot> slots;
   HostStage *hs = nullptr;      // of_pairs_run_host staging (lazily created)
   PairPool *pool = nullptr;     // of_pairs_open streaming batch (lanes of its own)
-  Session *session[SES_KINDS] = {};  // of_tracks_open, of_denoise_open, of_stab_open, of_sr_open, of_inpaint_open, of_masks_open: one of each
+  Session *session[SES_KINDS] = {};  // of_tracks_open, of_denoise_open, of_stab_open, of_sr_open, of_inpaint_open, of_masks_open, of_consist_open: one of each
   std::vector<of_ctx *> lanes;  // of_pairs_run pipelines: own stream, arena and solver state
   Token big_own;                // (parent) the big-phase token its lanes share
   Token *big = nullptr;         // (lane) token held through phases of >= big_px pixels

@@ -1,6 +1,6 @@
 // host_session.hip — what the frame-sequence sessions of a context (point
 // tracker, temporal denoiser, stabiliser, super-resolver, inpainter, mask
-// propagator: Session, host_core.h) share: the
+// propagator, temporal consistency: Session, host_core.h) share: the
 // words of their messages, lookup and free, the open and push prologues, the
 // bookkeeping of the delayed emitters and the switch to reduced-resolution
 // pairs (of_session_set_flow_scale).
@@ -15,7 +15,8 @@ const SessionKind SESSION_KIND[SES_KINDS] = {{"point tracker", "of_tracks_", "po
                                              {"stabiliser", "of_stab_", "global motion"},
                                              {"super-resolver", "of_sr_", "super-resolution"},
                                              {"inpainter", "of_inpaint_", "video inpainting"},
-                                             {"mask propagator", "of_masks_", "mask propagation"}};
+                                             {"mask propagator", "of_masks_", "mask propagation"},
+                                             {"temporal consistency session", "of_consist_", "temporal consistency"}};
 
 std::string session_not_open(int kind) {
   const SessionKind &K = SESSION_KIND[kind];

@@ -16,6 +16,7 @@ from optical_flow.inpaint import (grow_mask, pair_weight, propagate_fill, VideoI
                                   INPAINT_SPATIAL)
 from optical_flow.masks import (advance_mask, MaskPropagator, propagate_masks, MASK_CARRIED, MASK_VOTED, MASK_UNKNOWN,
                                 MASK_GIVEN)
+from optical_flow.consistency import screened_poisson, consistency_step, TemporalConsistency, consistent_frames
 from optical_flow.noise import estimate_noise, NoiseEstimate
 from optical_flow.motion import (fit_motion, warp_affine, Stabilizer, stabilize_frames, MotionFit, segment_motion,
                                  MotionLayers, MotionLayer, LAYER_NONE)
@@ -39,4 +40,5 @@ __all__ = ['estimate_flow', 'estimate_flow_batch', 'PairStream', 'read_flo', 'wr
            'reduce_frame', 'upsample_flow', 'fuse_weights', 'super_resolve', 'SuperResolver', 'super_resolve_frames',
            'grow_mask', 'pair_weight', 'propagate_fill', 'VideoInpainter', 'inpaint_frames', 'INPAINT_KEPT',
            'INPAINT_FILLED', 'INPAINT_UNFILLED', 'advance_mask', 'MaskPropagator', 'propagate_masks', 'MASK_CARRIED',
-           'MASK_VOTED', 'MASK_UNKNOWN', 'MASK_GIVEN', 'poisson_fill', 'blend_fill', 'INPAINT_SPATIAL']
+           'MASK_VOTED', 'MASK_UNKNOWN', 'MASK_GIVEN', 'poisson_fill', 'blend_fill', 'INPAINT_SPATIAL', 'screened_poisson',
+           'consistency_step', 'TemporalConsistency', 'consistent_frames']

@@ -244,6 +244,15 @@ class OfMaskOpts(C.Structure):
                 ("alpha2", C.c_double)]
 
 
+# blind temporal consistency (include/optflow.h, "Blind temporal consistency")
+CONSIST_CYCLES = 5
+CONSIST_MAX_CHANNELS = 4
+
+
+class OfConsistOpts(C.Structure):
+    _fields_ = [("fuse", OfFuseOpts), ("solve", OfBlendOpts), ("lambda_", C.c_double)]
+
+
 def penalty(kind, p0=1.0, p1=0.0):
     return OfPenalty(PENALTY[kind], 0, float(p0), float(p1))
 

@@ -12,7 +12,7 @@ import numpy as np
 
 from optical_flow._abi import (OfParams, OfStats, OfCgGeometry, OfSolveRecord, OfProgressFn, OfTrackOpts, OfFuseOpts,
                                OfNoiseEstimate, OfMotionOpts, OfMotionFit, OfStabOpts, OfLayersOpts, OfMotionLayer,
-                               OfUpsampleOpts, OfSrOpts, OfInpaintOpts, OfMaskOpts, OfBlendOpts, OF_ABI_VERSION,
+                               OfUpsampleOpts, OfSrOpts, OfInpaintOpts, OfMaskOpts, OfBlendOpts, OfConsistOpts, OF_ABI_VERSION,
                                OF_EINVAL, OF_ENOTSUP)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -162,6 +162,13 @@ _SIGS = {
     "of_masks_open": ([_vp, C.POINTER(OfParams), C.c_int, C.c_int, C.c_int, C.POINTER(OfMaskOpts)], C.c_int),
     "of_masks_push": ([_vp, _fp, _u8p, _u8p, _u8p], C.c_int),
     "of_masks_close": ([_vp], C.c_int),
+    "of_screened_solve": ([_vp, _fp, _dp, _dp, C.c_int, C.c_int, C.c_int, C.POINTER(OfBlendOpts), _dp], C.c_int),
+    "of_consist_step": ([_vp, _fp, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp, C.c_int, _fp, _u8p,
+                         C.POINTER(OfConsistOpts), _fp, _fp], C.c_int),
+    "of_consist_open": ([_vp, C.POINTER(OfParams), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(OfConsistOpts)],
+                        C.c_int),
+    "of_consist_push": ([_vp, _fp, _fp, _fp, _fp], C.c_int),
+    "of_consist_close": ([_vp], C.c_int),
     "of_poisson_solve": ([_vp, _u8p, _fp, _fp, _u8p, C.c_int, C.c_int, C.c_int, C.POINTER(OfBlendOpts), _dp], C.c_int),
     "of_inpaint_blend": ([_vp, _fp, _u8p, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                           C.POINTER(OfInpaintOpts), C.POINTER(OfBlendOpts), _fp, _u8p], C.c_int),
